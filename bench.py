@@ -12,10 +12,22 @@ Workloads (BASELINE.json configs):
   c2  configs[1]: msg "bradfitz" (8 B), nonces [0, 2^32) per GPU, one SHA-256
       compression per nonce.
   c3  configs[2]: 120-byte msg (host midstate), [0, 2^34) per GPU, 2 tail blocks.
-At N = 1 the line also carries c2 and c3 as timed sub-results (`by_config`),
-each checked against its independently pinned answer.
 A step is one full scan of the job (the drop-in for miner.go:56-63) ending
 with the (hash, nonce) result on the host.
+
+A plain run does only what the headline figure needs: set up, W warm-up
+steps, K timed steps, the result line (with the roofline fractions computed
+from the timed steps' own HIP events and the committed profiles).
+  --dump-outputs DIR  after the timed steps, write what the last one returned
+      to its caller as DIR/hash.npy and DIR/nonce.npy (dump_outputs).  The job
+      is fixed by the arguments, so two builds can be compared file for file.
+  --full  everything else the benchmark measures, after the timed steps and
+      never inside them: at N = 1 c2 and c3 as timed sub-results
+      (`by_config`), each checked against its independently pinned answer;
+      the shader-clock stamps around the timed steps (`roofline.clock`);
+      configs[0]'s request latency (`small_request`); the CPU baseline
+      (`cpu_baseline`).  --no-cpu, --no-by-config and --no-small-request drop
+      one of them from a --full run.
 
 Production settings only: the library's test knobs (P1HIP_*, honoured only
 under P1HIP_TEST_KNOBS=1) must be off -- bench.py exits 4 before timing
@@ -808,7 +820,20 @@ def timed_steps(step, steps, warmup, barrier, progress=None, probe=None):
     return elapsed, step_ms, results, p1_amd.get_stats(), clock
 
 
-# by_config sub-results of the N = 1 line: (config, warmup, steps)
+def dump_outputs(out_dir, result):
+    """--dump-outputs: the (hash, nonce) pair the last timed step returned to
+    its caller, as <out_dir>/hash.npy and <out_dir>/nonce.npy.  Both are unsigned
+    64-bit values, which float64 does not hold exactly, so each file is a
+    float64 array [high 32 bits, low 32 bits]: exact, and comparable element
+    for element between two builds."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in (("hash", int(result[0])), ("nonce", int(result[1]))):
+        np.save(os.path.join(out_dir, name + ".npy"), np.array([v >> 32, v & 0xFFFFFFFF], dtype=np.float64))
+
+
+# by_config sub-results of the N = 1 --full line: (config, warmup, steps)
 SUB_CONFIGS = [("c2", 2, 5), ("c3", 1, 3)]
 
 
@@ -852,13 +877,20 @@ def main():
     ap.add_argument("--layout", default=None, metavar="L,START[,N]",
                     help="profile one tail layout instead of a BASELINE config (tools/sweep.py message of L bytes, "
                          "nonces [START, START+N), N default 2^32)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the last step's (hash, nonce) result as DIR/hash.npy and "
+                         "DIR/nonce.npy (float64 [high 32 bits, low 32 bits] each)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what the headline does not need: the c2/c3 "
+                         "sub-results at N = 1, the shader clock around the timed steps, the small-request "
+                         "latency and the CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--no-small-request", action="store_true",
-                    help="skip the configs[0]-sized latency probe (profiling runs: keeps every "
+                    help="--full without the configs[0]-sized latency probe (profiling runs: keeps every "
                          "k_scan launch in the rocprof summary a workload launch)")
     ap.add_argument("--no-by-config", action="store_true",
-                    help="skip the c2/c3 sub-results of the N = 1 line (profiling runs)")
+                    help="--full without the c2/c3 sub-results of the N = 1 line (profiling runs)")
     ap.add_argument("--dist", action="store_true",
                     help="take the one-process-per-GPU torch.distributed path even when WORLD_SIZE is 1 "
                          "(rehearses the driver's N>1 launch, RCCL included, on one GPU)")
@@ -936,9 +968,11 @@ def main():
             sys.exit(5)
     init_ms = (time.perf_counter() - t_init) * 1e3
     codeobj = p1_amd.codeobj_sha256()
-    # HIP ordinals of the devices this process scans on, for the clock probe
-    ordinals = [gpu] if mode == "torchrun" else [p1_amd.device_info(i)["ordinal"] for i in devices]
-    probe = ClockProbe(ordinals)
+    probe = None
+    if args.full:
+        # HIP ordinals of the devices this process scans on, for the clock probe
+        ordinals = [gpu] if mode == "torchrun" else [p1_amd.device_info(i)["ordinal"] for i in devices]
+        probe = ClockProbe(ordinals)
 
     timing = {}  # torchrun: this rank's scan / all-gather time of the timed steps
 
@@ -1000,6 +1034,8 @@ def main():
     known, known_src = known_answer(cfg, n_gpus)
 
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, result)
         hashes = total * args.steps
         value = hashes / elapsed / 1e9
         ms_per_step = elapsed * 1e3 / args.steps
@@ -1027,6 +1063,7 @@ def main():
             "n_gpus": n_gpus,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": ms_per_step,
             # SURVEY.md 8(d) timing: per-step wall times (first enqueue to the
             # host min) of this rank, median of the K steps; one-time setup
@@ -1064,7 +1101,7 @@ def main():
         }
         if "layout" in cfg:
             line["config"].update(layout=cfg["layout"], variant=cfg["variant"], b_tail=cfg["b_tail"])
-        if n_gpus == 1 and mode != "torchrun" and not args.no_by_config and "layout" not in cfg:
+        if args.full and n_gpus == 1 and mode != "torchrun" and not args.no_by_config and "layout" not in cfg:
             # the other BASELINE configs on the same GPU, after the timed
             # headline run (never inside it)
             line["by_config"] = {run["config"]: {"value": value, "ms_per_step": ms_per_step,
@@ -1082,7 +1119,7 @@ def main():
         # configs[0]'s request (client 'bradfitz' maxNonce 9999) as one
         # drop-in call: per-request latency of p1hip_scan on a small job
         lat = []
-        for _ in range(0 if args.no_small_request else 20):
+        for _ in range(20 if args.full and not args.no_small_request else 0):
             t0 = time.perf_counter()
             small = p1_amd.scan(b"bradfitz", 0, 9999)
             lat.append(time.perf_counter() - t0)
@@ -1091,7 +1128,7 @@ def main():
             line["small_request"] = {"request": "bradfitz [0, 9999] (configs[0])", "result": list(small),
                                      "matches_known": tuple(small) == (1419516646206828, 9898),
                                      "median_latency_us": lat[len(lat) // 2] * 1e6}
-        if n_gpus == 1 and not args.no_cpu:
+        if args.full and n_gpus == 1 and not args.no_cpu:
             print("bench.py: cpu_baseline", file=sys.stderr, flush=True)
             line["cpu_baseline"] = cpu_baseline(msg, 1 << 31, args.cpu_seconds)
         print(json.dumps(line), flush=True)

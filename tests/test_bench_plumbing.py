@@ -392,6 +392,25 @@ def test_the_built_code_object_has_committed_profiles():
     assert e["one_gpu_source"] == bench.rocprof_row("c4", sha)[1]
 
 
+def test_dump_outputs_holds_the_result_exactly(tmp_path):
+    """--dump-outputs: the (hash, nonce) of the last timed step as float64
+    [high 32 bits, low 32 bits] arrays -- exact for any u64, where one
+    float64 per value would round a hash above 2^53."""
+    import numpy as np
+
+    res = (0xFEDCBA9876543211, (1 << 38) - 1)
+    out = tmp_path / "dump" / "run1"  # created on demand
+    bench.dump_outputs(str(out), res)
+    assert sorted(p.name for p in out.iterdir()) == ["hash.npy", "nonce.npy"]
+    for name, want in zip(("hash", "nonce"), res):
+        a = np.load(out / (name + ".npy"))
+        assert a.dtype == np.float64 and a.shape == (2,)
+        assert (int(a[0]) << 32) | int(a[1]) == want
+    # the same result writes the same bytes: two builds compare file for file
+    bench.dump_outputs(str(tmp_path / "again"), res)
+    assert (out / "hash.npy").read_bytes() == (tmp_path / "again" / "hash.npy").read_bytes()
+
+
 def test_layout_config_profiles_one_tail_layout():
     """--layout L,START[,N]: sweep.py's message, one decade, no pinned answer;
     a range that crosses a decade (two kernel variants) is refused."""

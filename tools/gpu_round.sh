@@ -21,10 +21,10 @@ step() {  # step <name> <timeout> <cmd...>
 [ "${RUN_MIX:-0}" != 1 ] || step valu_mix 300 "$ROOT/tools/valu_mix" > "$OUT/${TAG}_valu_mix.jsonl"
 [ "${SKIP_TESTS:-0}" = 1 ] || step pytest_gpu 900 python -u -m pytest "$ROOT/tests" -m gpu -x -v -rP -p no:cacheprovider --timeout 300 --timeout-method thread ${PYTEST_K:+-k "$PYTEST_K"} > "$OUT/${TAG}_pytest_gpu.log" 2>&1
 [ "${SKIP_SMOKE:-0}" = 1 ] || step smoke 300 python -c "import sys; sys.path.insert(0, '$ROOT'); import __graft_entry__ as g; g.smoke()" > "$OUT/${TAG}_smoke.log" 2>&1
-[ "${SKIP_BENCH:-0}" = 1 ] || step bench 600 python "$ROOT/bench.py" ${BENCH_ARGS:-} > "$OUT/${TAG}_bench.json" 2> "$OUT/${TAG}_bench.err"
-[ -z "${EXTRA_BENCH:-}" ] || step bench_extra 600 python "$ROOT/bench.py" $EXTRA_BENCH > "$OUT/${TAG}_bench_extra.json" 2> "$OUT/${TAG}_bench_extra.err"
+[ "${SKIP_BENCH:-0}" = 1 ] || step bench 600 python "$ROOT/bench.py" --full ${BENCH_ARGS:-} > "$OUT/${TAG}_bench.json" 2> "$OUT/${TAG}_bench.err"
+[ -z "${EXTRA_BENCH:-}" ] || step bench_extra 600 python "$ROOT/bench.py" --full $EXTRA_BENCH > "$OUT/${TAG}_bench_extra.json" 2> "$OUT/${TAG}_bench_extra.err"
 for cfg in ${BENCH_CONFIGS:-}; do
-  step bench_$cfg 600 python "$ROOT/bench.py" --config $cfg --steps ${CFG_STEPS:-3} --warmup 1 --no-cpu --no-by-config > "$OUT/${TAG}_bench_$cfg.json" 2> "$OUT/${TAG}_bench_$cfg.err"
+  step bench_$cfg 600 python "$ROOT/bench.py" --full --config $cfg --steps ${CFG_STEPS:-3} --warmup 1 --no-cpu --no-by-config > "$OUT/${TAG}_bench_$cfg.json" 2> "$OUT/${TAG}_bench_$cfg.err"
 done
 [ "${RUN_SWEEP:-0}" != 1 ] || step sweep 900 python "$ROOT/tools/sweep.py" > "$OUT/${TAG}_sweep.jsonl" 2> "$OUT/${TAG}_sweep.err"
 [ "${RUN_SERVER:-0}" != 1 ] || step bench_server 900 python "$ROOT/tools/bench_server.py" > "$OUT/${TAG}_bench_server.json" 2> "$OUT/${TAG}_bench_server.err"
@@ -40,16 +40,16 @@ if [ "${RUN_SHARD_BALANCE:-0}" = 1 ]; then
 fi
 if [ "${RUN_TORCHRUN8:-0}" = 1 ]; then
   # the driver's N = 8 launch shape on one GPU: 8 ranks, gloo all-gather
-  step torchrun8 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29513 "$ROOT/bench.py" --gpus 8 --steps 2 --warmup 1 --dist-backend gloo > "$OUT/${TAG}_torchrun8.json" 2> "$OUT/${TAG}_torchrun8.err"
+  step torchrun8 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29513 "$ROOT/bench.py" --full --gpus 8 --steps 2 --warmup 1 --dist-backend gloo > "$OUT/${TAG}_torchrun8.json" 2> "$OUT/${TAG}_torchrun8.err"
 fi
 if [ "${RUN_TORCHRUN:-0}" = 1 ]; then
   # rehearse the N>1 launch path on one GPU: 2 ranks, gloo all-gather, shared device
-  step torchrun2 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29511 "$ROOT/bench.py" --gpus 2 --steps 2 --warmup 1 --dist-backend gloo > "$OUT/${TAG}_torchrun2.json" 2> "$OUT/${TAG}_torchrun2.err"
+  step torchrun2 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29511 "$ROOT/bench.py" --full --gpus 2 --steps 2 --warmup 1 --dist-backend gloo > "$OUT/${TAG}_torchrun2.json" 2> "$OUT/${TAG}_torchrun2.err"
 fi
 if [ "${RUN_DIST1:-0}" = 1 ]; then
   # the driver's N>1 code path (torch.distributed "nccl" = RCCL, device_id,
   # all-gather of the 16-B partials, all-reduce of the step time) at world 1
-  step dist1_nccl 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29512 "$ROOT/bench.py" --gpus 1 --dist --config c4 --steps 2 --warmup 1 --no-cpu > "$OUT/${TAG}_dist1_nccl.json" 2> "$OUT/${TAG}_dist1_nccl.err"
+  step dist1_nccl 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29512 "$ROOT/bench.py" --full --gpus 1 --dist --config c4 --steps 2 --warmup 1 --no-cpu > "$OUT/${TAG}_dist1_nccl.json" 2> "$OUT/${TAG}_dist1_nccl.err"
 fi
 # configs[4] end to end over LSP (tools/bench_lsp.py), one run per spec
 # "name:VAR=v,VAR=v" (MINERS, COPIES, EPOCH_MS, REPS, HEDGE ...)
@@ -60,7 +60,7 @@ for spec in ${LSP_RUNS:-}; do
 done
 for lib in ${VARIANTS:-}; do
   n=$(basename "$lib" .so)
-  P1HIP_LIB="$ROOT/$lib" step "bench_$n" 600 python "$ROOT/bench.py" --steps 5 --warmup 1 --no-cpu --no-by-config > "$OUT/${TAG}_bench_$n.json" 2> "$OUT/${TAG}_bench_$n.err"
+  P1HIP_LIB="$ROOT/$lib" step "bench_$n" 600 python "$ROOT/bench.py" --full --steps 5 --warmup 1 --no-cpu --no-by-config > "$OUT/${TAG}_bench_$n.json" 2> "$OUT/${TAG}_bench_$n.err"
 done
 if [ "${RUN_ASAN_TEARDOWN:-0}" = 1 ]; then
   # whose free trips ROCm ASan's "!dev_runtime_unloaded_"
@@ -90,7 +90,7 @@ prof_one() {  # prof_one <name> <bench job args...>
     # the kernel trace of a bench run shaped like the timed one (warm-up
     # steps, then timed steps): summarize_prof --skip-launches 2 averages the
     # same launches bench.py's own HIP events time
-    step rocprof_stats_$name 600 rocprofv3 --kernel-trace --stats -d "$OUT/${TAG}_${name}_prof" -o run --output-format csv -- python3 "$ROOT/bench.py" --steps ${PROF_STEPS:-3} --warmup 2 --no-cpu --no-small-request --no-by-config "$@" > "$OUT/${TAG}_${name}_prof_bench.json"
+    step rocprof_stats_$name 600 rocprofv3 --kernel-trace --stats -d "$OUT/${TAG}_${name}_prof" -o run --output-format csv -- python3 "$ROOT/bench.py" --full --steps ${PROF_STEPS:-3} --warmup 2 --no-cpu --no-small-request --no-by-config "$@" > "$OUT/${TAG}_${name}_prof_bench.json"
   fi
   if [ "${SKIP_PMC:-0}" != 1 ]; then
     local i=0 set
@@ -99,7 +99,7 @@ prof_one() {  # prof_one <name> <bench job args...>
                "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_IFETCH" \
                "FETCH_SIZE" "WRITE_SIZE"; do
       i=$((i+1))
-      step pmc_${name}_$i 300 rocprofv3 --pmc $set --kernel-include-regex '^k_scan$' -d "$OUT/${TAG}_${name}_pmc$i" -o pmc --output-format csv -- python3 "$ROOT/bench.py" --steps 1 --warmup 0 --no-cpu --no-small-request --no-by-config "$@" > "$OUT/${TAG}_${name}_pmc${i}_bench.json"
+      step pmc_${name}_$i 300 rocprofv3 --pmc $set --kernel-include-regex '^k_scan$' -d "$OUT/${TAG}_${name}_pmc$i" -o pmc --output-format csv -- python3 "$ROOT/bench.py" --full --steps 1 --warmup 0 --no-cpu --no-small-request --no-by-config "$@" > "$OUT/${TAG}_${name}_pmc${i}_bench.json"
     done
   fi
 }
