@@ -5,7 +5,7 @@ HIPFLAGS ?= -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -Wall
 LLVM ?= /opt/rocm/lib/llvm/bin
 CSRC := p1_amd/csrc
 HDRS := $(CSRC)/sha256_dev.hpp $(CSRC)/scan_core.hpp $(CSRC)/planner.hpp $(CSRC)/fast_variants.inc $(CSRC)/variant_cost.inc \
-        $(CSRC)/scan_abi.hpp include/p1hip.h
+        $(CSRC)/scan_abi.hpp $(CSRC)/batch_abi.hpp $(CSRC)/batch_plan.hpp include/p1hip.h
 # what the device code includes (the host-side planner does not rebuild it)
 DEVHDRS := $(CSRC)/sha256_dev.hpp $(CSRC)/scan_core.hpp $(CSRC)/fast_variants.inc $(CSRC)/scan_abi.hpp
 # device code: HIP C++ -> gfx950 assembly -> tools/isa_post.py post-pass
@@ -28,7 +28,7 @@ DEVFLAGS ?= -O3 -std=c++17 --offload-arch=$(ARCH) --cuda-device-only -Wall -mllv
 ISAPOST ?= --no-e64 --align-loops=3 --loop-offset=4 --pair-sched=0 --sched-amax=5 --sched-bmax=4 --strict-hazards --prio=0,1
 BUILD := build
 
-all: p1_amd/libp1hip.so oracle tools/p1emu p1_amd/p1miner p1_amd/p1server p1_amd/p1client tools/lsp_scenarios \
+all: p1_amd/libp1hip.so oracle tools/p1emu tools/batch_emu p1_amd/p1miner p1_amd/p1server p1_amd/p1client tools/lsp_scenarios \
      tools/lsp_fake_miner tools/queue_ctl tools/wcal tools/vbank tools/libp1clock.so
 
 # The assembly and object stages are intermediates: once the code object
@@ -51,11 +51,33 @@ $(BUILD)/p1hip_kernels.hsaco: $(BUILD)/p1hip_kernels.o
 $(BUILD)/p1hip_kernels_blob.o: $(CSRC)/p1hip_kernels_blob.S $(BUILD)/p1hip_kernels.hsaco
 	gcc -c -fPIC -DP1HIP_KERNELS_CO='"$(CURDIR)/$(BUILD)/p1hip_kernels.hsaco"' -o $@ $<
 
+# The batch kernels (p1hip_scan_batch): a second, small code object with only
+# the generic per-thread path, so no post-pass and a compile of seconds.  Its
+# blob is linked AFTER the scan object's: the scan object stays the first
+# AMDGPU ELF in libp1hip.so (tests/test_codeobj.py).
+BATCHDEVHDRS := $(CSRC)/sha256_dev.hpp $(CSRC)/scan_core.hpp $(CSRC)/scan_abi.hpp $(CSRC)/batch_abi.hpp
+BATCHDEVFLAGS ?= -O3 -std=c++17 --offload-arch=$(ARCH) --cuda-device-only -Wall
+.SECONDARY: $(BUILD)/p1hip_batch.s $(BUILD)/p1hip_batch.o
+$(BUILD)/p1hip_batch.s: $(CSRC)/p1hip_batch_kernels.hip $(BATCHDEVHDRS)
+	mkdir -p $(BUILD)
+	$(HIPCC) $(BATCHDEVFLAGS) -S -o $@ $(CSRC)/p1hip_batch_kernels.hip
+
+$(BUILD)/p1hip_batch.o: $(BUILD)/p1hip_batch.s
+	$(LLVM)/clang -cc1as -triple amdgcn-amd-amdhsa -filetype obj -target-cpu $(ARCH) -mrelocation-model pic -o $@ $<
+
+$(BUILD)/p1hip_batch.hsaco: $(BUILD)/p1hip_batch.o
+	$(LLVM)/ld.lld -m elf64_amdgpu --no-undefined -shared -o $@ $<
+
+$(BUILD)/p1hip_batch_blob.o: $(CSRC)/p1hip_batch_blob.S $(BUILD)/p1hip_batch.hsaco
+	gcc -c -fPIC -DP1HIP_BATCH_CO='"$(CURDIR)/$(BUILD)/p1hip_batch.hsaco"' -o $@ $<
+
+BLOBS := $(BUILD)/p1hip_kernels_blob.o $(BUILD)/p1hip_batch_blob.o
+
 $(BUILD)/p1hip_host.o: $(CSRC)/p1hip.hip $(HDRS)
 	mkdir -p $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c -o $@ $(CSRC)/p1hip.hip
 
-p1_amd/libp1hip.so: $(BUILD)/p1hip_host.o $(BUILD)/p1hip_kernels_blob.o
+p1_amd/libp1hip.so: $(BUILD)/p1hip_host.o $(BLOBS)
 	$(HIPCC) -shared -fPIC -o $@ $^ -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
 
 # C++ host mirror of the reference's bitcoin package, LSP transport and the
@@ -109,6 +131,11 @@ tools/vbank: tools/vbank.hip
 tools/p1emu: tools/p1emu.cpp $(HDRS)
 	$(HIPCC) -O2 -std=c++17 -DP1_NV2_PLAIN -o $@ tools/p1emu.cpp
 
+# host-only replay of a p1hip_scan_batch call: the library's own table builder
+# and segment lookup, generic_thread per thread, the per-request fold
+tools/batch_emu: tools/batch_emu.cpp $(HDRS)
+	$(HIPCC) -O2 -std=c++17 -o $@ tools/batch_emu.cpp
+
 oracle:
 	$(MAKE) -C oracle
 
@@ -126,7 +153,7 @@ SAN_tsan := -fsanitize=thread
 SANDIR := $(BUILD)/san
 SANPROGS := lsp_scenarios sched_test p1server p1client lsp_fake_miner
 sanitize: $(foreach s,asan tsan,$(addprefix $(SANDIR)/$(s)/,$(SANPROGS)))
-sanitize-emu: $(SANDIR)/asan/p1emu
+sanitize-emu: $(SANDIR)/asan/p1emu $(SANDIR)/asan/batch_emu
 
 $(SANDIR)/%/lsp_scenarios: tests/lsp/lsp_scenarios.cpp p1_amd/host/lsp.cpp p1_amd/host/lspnet.cpp p1_amd/host/lsp_message.cpp $(HOSTHDR)
 	mkdir -p $(@D)
@@ -155,7 +182,7 @@ $(SANLIB)/p1hip_host.o: $(CSRC)/p1hip.hip $(HDRS)
 	mkdir -p $(@D)
 	$(HIPCC) -O1 -g -std=c++17 -fPIC --offload-arch=$(ARCH) -fno-omit-frame-pointer -Xarch_host -fsanitize=address \
 	    -Xarch_host -fsanitize=undefined -Xarch_host -fno-sanitize-recover=undefined -c -o $@ $(CSRC)/p1hip.hip
-$(SANLIB)/libp1hip.so: $(SANLIB)/p1hip_host.o $(BUILD)/p1hip_kernels_blob.o
+$(SANLIB)/libp1hip.so: $(SANLIB)/p1hip_host.o $(BLOBS)
 	$(HIPCC) -shared -fPIC -o $@ $^ -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
 $(SANLIB)/capi_san_stress: tests/capi_san_stress.cpp include/p1hip.h $(SANLIB)/libp1hip.so oracle
 	$(SANCXX) $(SANBASE) $(SAN_asan) -Iinclude -o $@ tests/capi_san_stress.cpp -L$(SANLIB) -lp1hip \
@@ -174,7 +201,7 @@ $(SANLIB)/tsan/p1hip_host.o: $(CSRC)/p1hip.hip $(HDRS)
 	mkdir -p $(@D)
 	$(HIPCC) -O1 -g -std=c++17 -fPIC --offload-arch=$(ARCH) -fno-omit-frame-pointer -Xarch_host -fsanitize=thread \
 	    -c -o $@ $(CSRC)/p1hip.hip
-$(SANLIB)/tsan/libp1hip.so: $(SANLIB)/tsan/p1hip_host.o $(BUILD)/p1hip_kernels_blob.o
+$(SANLIB)/tsan/libp1hip.so: $(SANLIB)/tsan/p1hip_host.o $(BLOBS)
 	$(HIPCC) -shared -fPIC -o $@ $^ -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
 $(SANLIB)/tsan/capi_san_stress: tests/capi_san_stress.cpp include/p1hip.h $(SANLIB)/tsan/libp1hip.so oracle
 	$(SANCXX) $(SANBASE) $(SAN_tsan) -Iinclude -o $@ tests/capi_san_stress.cpp -L$(SANLIB)/tsan -lp1hip \
@@ -184,6 +211,11 @@ $(SANDIR)/asan/p1emu: tools/p1emu.cpp $(HDRS)
 	mkdir -p $(@D)
 	$(HIPCC) -O1 -g -std=c++17 -fno-omit-frame-pointer -Xarch_host -fsanitize=address -Xarch_host -fsanitize=undefined \
 	    -Xarch_host -fno-sanitize-recover=undefined -DP1_NV2_PLAIN -o $@ tools/p1emu.cpp
+
+$(SANDIR)/asan/batch_emu: tools/batch_emu.cpp $(HDRS)
+	mkdir -p $(@D)
+	$(HIPCC) -O1 -g -std=c++17 -fno-omit-frame-pointer -Xarch_host -fsanitize=address -Xarch_host -fsanitize=undefined \
+	    -Xarch_host -fno-sanitize-recover=undefined -o $@ tools/batch_emu.cpp
 
 # libFuzzer harness of the wire codecs (tests/fuzz/fuzz_codecs.cpp) with
 # ASan + UBSan.  -asan-globals=0: with -fsanitize=fuzzer this clang registers
@@ -205,9 +237,9 @@ $(SANDIR)/fuzz_codecs: tests/fuzz/fuzz_codecs.cpp p1_amd/host/bitcoin.cpp p1_amd
 #   make variant NAME=x DEVEXTRA='-DP1_FAST_WAVES=5' ISAPOST='--no-e64'
 #   make variant NAME=nv2 DEVEXTRA=-DP1_NV2_PLAIN HOSTEXTRA=-DP1_NV2_PLAIN   (+ P1HIP_NO_SPLIT=1 at run time)
 variant:
-	$(MAKE) BUILD=build/var_$(NAME) DEVEXTRA="$(DEVEXTRA)" HIPFLAGS="$(HIPFLAGS) $(HOSTEXTRA)" ISAPOST="$(ISAPOST)" build/var_$(NAME)/p1hip_kernels_blob.o build/var_$(NAME)/p1hip_host.o
+	$(MAKE) BUILD=build/var_$(NAME) DEVEXTRA="$(DEVEXTRA)" HIPFLAGS="$(HIPFLAGS) $(HOSTEXTRA)" ISAPOST="$(ISAPOST)" build/var_$(NAME)/p1hip_kernels_blob.o build/var_$(NAME)/p1hip_batch_blob.o build/var_$(NAME)/p1hip_host.o
 	mkdir -p p1_amd/variants
-	$(HIPCC) -shared -fPIC -o p1_amd/variants/libp1hip_$(NAME).so build/var_$(NAME)/p1hip_host.o build/var_$(NAME)/p1hip_kernels_blob.o -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
+	$(HIPCC) -shared -fPIC -o p1_amd/variants/libp1hip_$(NAME).so build/var_$(NAME)/p1hip_host.o build/var_$(NAME)/p1hip_kernels_blob.o build/var_$(NAME)/p1hip_batch_blob.o -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
 
 # ISA + resource report of the scan kernels (for DESIGN.md / profiling):
 # build/p1hip_kernels.post.s is the exact assembly that ships
@@ -215,7 +247,7 @@ isa: $(BUILD)/p1hip_kernels.post.s
 	$(HIPCC) $(DEVFLAGS) -c -o /dev/null $(CSRC)/p1hip_kernels.hip -Rpass-analysis=kernel-resource-usage 2> $(BUILD)/resource.txt || true
 
 clean:
-	rm -f p1_amd/libp1hip.so tools/libp1clock.so tools/queue_ctl tools/p1emu p1_amd/p1miner p1_amd/p1server p1_amd/p1client tools/lsp_scenarios tools/lsp_fake_miner tools/wcal tools/vbank
-	rm -rf $(BUILD)/p1hip_kernels* $(BUILD)/p1hip_host.o
+	rm -f p1_amd/libp1hip.so tools/libp1clock.so tools/queue_ctl tools/p1emu tools/batch_emu p1_amd/p1miner p1_amd/p1server p1_amd/p1client tools/lsp_scenarios tools/lsp_fake_miner tools/wcal tools/vbank
+	rm -rf $(BUILD)/p1hip_kernels* $(BUILD)/p1hip_batch* $(BUILD)/p1hip_host.o
 	$(MAKE) -C oracle clean
 .PHONY: all oracle clean isa variant sanitize sanitize-emu sanitize-lib sanitize-lib-tsan fuzz

@@ -95,6 +95,53 @@ int p1hip_hash(const uint8_t *msg, size_t msg_len, uint64_t nonce, uint64_t *out
 int p1hip_reduce_pairs(const uint64_t *hashes, const uint64_t *nonces, size_t n,
                        uint64_t *out_hash, uint64_t *out_nonce);
 
+/* Many requests in one call.  A miner that serves many clients' small jobs,
+ * or a chunk loop over short ranges, is bound by launch and completion
+ * latency when it calls p1hip_scan once per request: a configs[0]-sized
+ * request fills a few percent of the device.  p1hip_scan_batch coalesces
+ * every non-empty request of at most 2^16 nonces -- of any messages -- into
+ * one launch pair per device (k_batch_scan: one workgroup per 256 nonces of
+ * any request; k_batch_reduce: one workgroup per request), with one stream
+ * synchronisation per launch pair; a launch pair holds up to 2^20 workgroups.
+ * Larger requests run one by one through the p1hip_scan path, empty ranges
+ * are answered on the host. */
+typedef struct { const uint8_t *msg; size_t msg_len; uint64_t lower, upper; } p1hip_request_t;
+typedef struct { uint64_t hash, nonce; } p1hip_result_t;
+
+/* out[i] is exactly what p1hip_scan(reqs[i]...) would return, for every i.
+ * Every request is validated (as by p1hip_scan) before anything is launched:
+ * a bad one gives P1HIP_ERR_ARGS, p1hip_last_error() names its index and
+ * `out` is left untouched, as it is after any other error.  n == 0 returns 0
+ * without initialising a device; otherwise lazy init as in p1hip_scan.  With
+ * several devices the coalesced requests are cut into contiguous groups of
+ * near-equal workgroup count, one per device (no RCCL: a request lives wholly
+ * on one device), all launched before any stream is synchronised. */
+int p1hip_scan_batch(const p1hip_request_t *reqs, size_t n, p1hip_result_t *out);
+
+/* Host only (no device): how a batch would be laid out over ndev devices.
+ * tiles[i]: workgroup tiles of request i (0: empty range, or run individually);
+ * device[i] / launch[i]: the device (index as for p1hip_get_device_stats) and
+ * that device's launch pair (from 0) its coalesced launch goes to (-1: empty
+ * or individual).  p1hip_scan_batch lays its requests out with the same
+ * function. */
+int p1hip_batch_layout(const p1hip_request_t *reqs, size_t n, int ndev,
+                       uint32_t *tiles, int32_t *device, int32_t *launch);
+
+/* Accounting of p1hip_scan_batch since p1hip_reset_stats.  Requests run
+ * individually also count in p1hip_stats_t as scans; coalesced ones only here. */
+typedef struct {
+  uint64_t calls;            /* p1hip_scan_batch calls that succeeded             */
+  uint64_t requests;         /* requests in them                                  */
+  uint64_t coalesced;        /* ... answered by a coalesced launch pair           */
+  uint64_t individual;       /* ... run one by one (more than 2^16 nonces)        */
+  uint64_t empty;            /* ... with lower > upper (answered on the host)     */
+  uint64_t launches;         /* launch pairs (k_batch_scan + k_batch_reduce)      */
+  uint64_t tiles;            /* workgroups of k_batch_scan                        */
+  uint64_t nonces;           /* nonces they hashed                                */
+  double wall_ms;            /* host wall time inside p1hip_scan_batch            */
+} p1hip_batch_stats_t;
+int p1hip_get_batch_stats(p1hip_batch_stats_t *out);   /* cleared by p1hip_reset_stats */
+
 /* Kernel-level accounting.  One p1hip_scan = one (rarely several) launch of
  * the scan kernel k_scan per device, covering every decade of the range; a
  * share of at most 2^16 nonces is one launch of k_scan_small instead (plan in
@@ -178,8 +225,10 @@ int p1hip_comm_info(int index, int *nranks, int *rank);
  * header checks p1hip_abi_version() == P1HIP_ABI_VERSION before reading any
  * p1hip_*_t the library fills in.  History: 4 = p1hip 0.4 (fast_kernel_ms
  * removed from p1hip_stats_t, so the fields after fast_alg_ops moved); 5 =
- * p1hip 0.5 (p1hip_comm_info and this query added; the structs are as in 4). */
-#define P1HIP_ABI_VERSION 5
+ * p1hip 0.5 (p1hip_comm_info and this query added; the structs are as in 4);
+ * 6 = p1hip 0.6 (p1hip_scan_batch, p1hip_batch_layout, p1hip_get_batch_stats
+ * and their structs added; no existing struct changed). */
+#define P1HIP_ABI_VERSION 6
 int p1hip_abi_version(void);
 
 const char *p1hip_last_error(void);

@@ -14,6 +14,9 @@ from ._lib import (  # noqa: F401
     init,
     init_devices,
     scan,
+    scan_batch,
+    batch_layout,
+    get_batch_stats,
     hash,
     reduce_pairs,
     plan_shards,
@@ -31,5 +34,6 @@ from ._lib import (  # noqa: F401
     version,
     codeobj_bytes,
     codeobj_sha256,
+    batch_codeobj_sha256,
 )
 from .sharding import shard_range, combine_keys  # noqa: F401

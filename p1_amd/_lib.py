@@ -63,6 +63,31 @@ class DeviceStats(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class Request(ctypes.Structure):
+    _fields_ = [("msg", ctypes.c_char_p), ("msg_len", ctypes.c_size_t), ("lower", U64), ("upper", U64)]
+
+
+class Result(ctypes.Structure):
+    _fields_ = [("hash", U64), ("nonce", U64)]
+
+
+class BatchStats(ctypes.Structure):
+    _fields_ = [
+        ("calls", U64),
+        ("requests", U64),
+        ("coalesced", U64),
+        ("individual", U64),
+        ("empty", U64),
+        ("launches", U64),
+        ("tiles", U64),
+        ("nonces", U64),
+        ("wall_ms", ctypes.c_double),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class DeviceInfo(ctypes.Structure):
     _fields_ = [
         ("ordinal", ctypes.c_int32),
@@ -93,6 +118,11 @@ SIGNATURES = [
     ("p1hip_init_devices", ctypes.c_int, [ctypes.POINTER(ctypes.c_int), ctypes.c_int]),
     ("p1hip_scan", ctypes.c_int,
      [ctypes.c_char_p, ctypes.c_size_t, U64, U64, ctypes.POINTER(U64), ctypes.POINTER(U64)]),
+    ("p1hip_scan_batch", ctypes.c_int, [ctypes.POINTER(Request), ctypes.c_size_t, ctypes.POINTER(Result)]),
+    ("p1hip_batch_layout", ctypes.c_int,
+     [ctypes.POINTER(Request), ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(ctypes.c_uint32),
+      ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
+    ("p1hip_get_batch_stats", ctypes.c_int, [ctypes.POINTER(BatchStats)]),
     ("p1hip_hash", ctypes.c_int, [ctypes.c_char_p, ctypes.c_size_t, U64, ctypes.POINTER(U64)]),
     ("p1hip_plan_shards", ctypes.c_int,
      [ctypes.c_char_p, ctypes.c_size_t, U64, U64, ctypes.c_int, ctypes.POINTER(U64), ctypes.POINTER(U64)]),
@@ -164,6 +194,60 @@ def scan(msg, lower, upper):
     return h.value, n.value
 
 
+def _requests(requests):
+    """(array of Request, the message bytes it borrows) for an iterable of
+    (msg, lower, upper)."""
+    rows = [(_bytes(m), int(lo), int(hi)) for m, lo, hi in requests]
+    arr = (Request * max(len(rows), 1))()
+    for r, (m, lo, hi) in zip(arr, rows):
+        r.msg, r.msg_len, r.lower, r.upper = m, len(m), lo, hi
+    return arr, rows
+
+
+def scan_batch(requests):
+    """p1hip_scan_batch: `requests` is an iterable of (msg, lower, upper), msg
+    as for scan(); returns [(hash, nonce)] in request order, each exactly what
+    scan(msg, lower, upper) returns.  Requests of at most 2^16 nonces share
+    one launch pair per device instead of paying one launch each."""
+    arr, rows = _requests(requests)
+    out = (Result * max(len(rows), 1))()
+    _check(load().p1hip_scan_batch(arr, len(rows), out))
+    return [(out[i].hash, out[i].nonce) for i in range(len(rows))]
+
+
+def batch_layout(requests, ndev):
+    """p1hip_batch_layout: how scan_batch would lay `requests` out over `ndev`
+    devices; one {"tiles", "device", "launch"} per request (tiles 0 and
+    device / launch -1: empty range, or run individually).  Host-only."""
+    arr, rows = _requests(requests)
+    n = len(rows)
+    tiles = (ctypes.c_uint32 * max(n, 1))()
+    device = (ctypes.c_int32 * max(n, 1))()
+    launch = (ctypes.c_int32 * max(n, 1))()
+    _check(load().p1hip_batch_layout(arr, n, int(ndev), tiles, device, launch))
+    return [{"tiles": tiles[i], "device": device[i], "launch": launch[i]} for i in range(n)]
+
+
+def get_batch_stats():
+    """Accounting of scan_batch since reset_stats (p1hip_get_batch_stats)."""
+    s = BatchStats()
+    _check(load().p1hip_get_batch_stats(ctypes.byref(s)))
+    return s.as_dict()
+
+
+def batch_codeobj_sha256(lib=None):
+    """sha256 (hex) of the second embedded code object, the batch kernels
+    (p1hip_batch_co .. p1hip_batch_co_end of csrc/p1hip_batch_blob.S)."""
+    import hashlib
+
+    lib = lib or load()
+    start = ctypes.addressof(ctypes.c_char.in_dll(lib, "p1hip_batch_co"))
+    end = ctypes.addressof(ctypes.c_char.in_dll(lib, "p1hip_batch_co_end"))
+    if end <= start:
+        raise P1HipError(-100, "embedded batch code object is empty")
+    return hashlib.sha256(ctypes.string_at(start, end - start)).hexdigest()
+
+
 def hash(msg, nonce):  # noqa: A001 - mirrors bitcoin.Hash
     m = _bytes(msg)
     h = U64()
@@ -226,7 +310,7 @@ def comm_info(index):
 
 
 # include/p1hip.h P1HIP_ABI_VERSION: the struct layouts this module declares
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 
 def abi_version():

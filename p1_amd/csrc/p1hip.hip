@@ -14,6 +14,11 @@
 // (p1hip_kernels_blob.S); each device loads it with hipModuleLoadData.
 // Several devices: contiguous shards, one host thread per device, RCCL
 // all-gather of the 16-byte results (ncclCommInitAll), host lexicographic min.
+//
+// p1hip_scan_batch: many small requests (of any messages) in one launch pair
+// per device, k_batch_scan + k_batch_reduce, from a second, small code object
+// (p1hip_batch_kernels.hip, p1hip_batch_blob.S); layout and tables come from
+// batch_plan.hpp, which tools/batch_emu shares.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
@@ -30,11 +35,13 @@
 #include <vector>
 
 #include "../../include/p1hip.h"
+#include "batch_plan.hpp"
 #include "planner.hpp"
 #include "scan_abi.hpp"
 
-// the embedded gfx950 code object (p1hip_kernels_blob.S)
+// the embedded gfx950 code objects (p1hip_kernels_blob.S, p1hip_batch_blob.S)
 extern "C" const unsigned char p1hip_kernels_co[];
+extern "C" const unsigned char p1hip_batch_co[];
 
 using namespace p1;
 
@@ -102,7 +109,8 @@ constexpr uint32_t kMaxLaunchBlocks = 1u << 22;
 const char* const kTestKnobs[] = {
     "P1HIP_SMALL_MAX_NONCES", "P1HIP_MAX_LAUNCH_BLOCKS", "P1HIP_MAX_SCAN_SPAN", "P1HIP_KWTAB_MAX_BYTES",
     "P1HIP_NO_RCCL",          "P1HIP_FORCE_RCCL",        "P1HIP_MIN_FAST_THREADS", "P1HIP_TEST_FAIL_DEVICE",
-    "P1HIP_NO_TABLE",         "P1HIP_NO_SPLIT",          "P1HIP_SCAN_GRID",
+    "P1HIP_NO_TABLE",         "P1HIP_NO_SPLIT",          "P1HIP_SCAN_GRID",        "P1HIP_BATCH_MAX_NONCES",
+    "P1HIP_BATCH_MAX_TILES",
 };
 
 bool test_knobs_on() {
@@ -134,6 +142,27 @@ uint64_t launch_block_limit() {
   return n;
 }
 
+// P1HIP_BATCH_MAX_NONCES (tests only, read per batch call): requests of at
+// most this many nonces are coalesced by p1hip_scan_batch (default and cap
+// kBatchMaxNonces; 0 runs every request individually).  It does not depend on
+// P1HIP_SMALL_MAX_NONCES.
+uint64_t batch_nonce_limit() {
+  const char* v = test_knob("P1HIP_BATCH_MAX_NONCES");
+  if (!v) return kBatchMaxNonces;
+  const uint64_t n = strtoull(v, nullptr, 10);
+  return n < kBatchMaxNonces ? n : kBatchMaxNonces;
+}
+
+// P1HIP_BATCH_MAX_TILES (tests only, read per batch call): tiles per launch
+// pair, so GPU tests run several launch pairs on small batches (batch_layout
+// raises it to the largest single request's tile count).
+uint64_t batch_tile_limit() {
+  const char* v = test_knob("P1HIP_BATCH_MAX_TILES");
+  const uint64_t n = v ? strtoull(v, nullptr, 10) : 0;
+  if (n == 0 || n >= kBatchMaxTiles) return kBatchMaxTiles;
+  return n;
+}
+
 struct Dev {
   int ordinal = -1;
   hipStream_t stream = nullptr;
@@ -153,6 +182,20 @@ struct Dev {
   uint32_t* d_scan_ticket = nullptr;  // k_scan's work queue: [tiles handed out, workgroups done] (0 between launches)
   uint32_t scan_grid = 0;       // k_scan workgroups the device holds at once (occupancy x CUs)
   bool small_used = false;      // this scan ran k_scan_small (result already in h_res[0])
+  // p1hip_scan_batch: its own code object and buffers (grown on demand, kept
+  // across calls; no p1hip_scan touches them)
+  hipModule_t bmod = nullptr;
+  hipFunction_t f_bscan = nullptr, f_breduce = nullptr;
+  BatchSeg* d_bseg = nullptr;   // segment table of one launch pair
+  BatchSeg* h_bseg = nullptr;   // pinned staging
+  size_t bseg_cap = 0;
+  uint32_t* d_btile0 = nullptr; // first tile of each request (+ end)
+  uint32_t* h_btile0 = nullptr; // pinned staging
+  Key* d_bout = nullptr;        // one Key per request
+  Key* h_bout = nullptr;        // pinned
+  size_t breq_cap = 0;          // requests the three above hold
+  Key* d_bpart = nullptr;       // one partial per tile
+  size_t bpart_cap = 0;
   std::vector<hipEvent_t> evs;  // profiling event pool (pairs)
   // MODE 5 K+W tables on this device, least recently used first (built by
   // k_kwtable; keyed by the block-1 template and k)
@@ -202,6 +245,7 @@ struct Runtime {
   bool tabulate = true;
   int fail_device = -1;
   p1hip_stats_t stats{};
+  p1hip_batch_stats_t bstats{};
 };
 
 // Never destroyed: the runtime state outlives every static destructor, so a
@@ -232,9 +276,17 @@ int dev_release(Dev& d) {
   if (d.d_small_part) (void)hipFree(d.d_small_part);
   if (d.d_ticket) (void)hipFree(d.d_ticket);
   if (d.d_scan_ticket) (void)hipFree(d.d_scan_ticket);
+  if (d.d_bseg) (void)hipFree(d.d_bseg);
+  if (d.h_bseg) (void)hipHostFree(d.h_bseg);
+  if (d.d_btile0) (void)hipFree(d.d_btile0);
+  if (d.h_btile0) (void)hipHostFree(d.h_btile0);
+  if (d.d_bout) (void)hipFree(d.d_bout);
+  if (d.h_bout) (void)hipHostFree(d.h_bout);
+  if (d.d_bpart) (void)hipFree(d.d_bpart);
   if (d.h_res) (void)hipHostFree(d.h_res);
   if (d.stream) (void)hipStreamDestroy(d.stream);
   if (d.mod) (void)hipModuleUnload(d.mod);
+  if (d.bmod) (void)hipModuleUnload(d.bmod);
   d = Dev();
   return 0;
 }
@@ -286,6 +338,9 @@ int init_devs(Runtime& R, const std::vector<int>& ords) {
     HIPCHK(hipModuleGetFunction(&d.f_pairs, d.mod, "k_pairs"));
     HIPCHK(hipModuleGetFunction(&d.f_small, d.mod, "k_scan_small"));
     HIPCHK(hipModuleGetFunction(&d.f_kwtable, d.mod, "k_kwtable"));
+    HIPCHK(hipModuleLoadData(&d.bmod, p1hip_batch_co));
+    HIPCHK(hipModuleGetFunction(&d.f_bscan, d.bmod, "k_batch_scan"));
+    HIPCHK(hipModuleGetFunction(&d.f_breduce, d.bmod, "k_batch_reduce"));
     HIPCHK(hipMalloc(&d.d_small_part, sizeof(Key) * kSmallMaxBlocks));
     HIPCHK(hipMalloc(&d.d_ticket, sizeof(uint32_t)));
     HIPCHK(hipMalloc(&d.d_scan_ticket, 2 * sizeof(uint32_t)));
@@ -677,6 +732,7 @@ Key finish_key(Key k) {
 
 int scan_locked(const uint8_t* msg, size_t msg_len, uint64_t lower, uint64_t upper, uint64_t* out_hash,
                 uint64_t* out_nonce);
+int scan_batch_locked(const p1hip_request_t* reqs, size_t n, p1hip_result_t* out);
 int reduce_pairs_locked(const uint64_t* hashes, const uint64_t* nonces, size_t n, uint64_t* out_hash,
                         uint64_t* out_nonce);
 
@@ -732,10 +788,10 @@ int p1hip_scan(const uint8_t* msg, size_t msg_len, uint64_t lower, uint64_t uppe
 
 namespace {
 
-int scan_locked(const uint8_t* msg, size_t msg_len, uint64_t lower, uint64_t upper, uint64_t* out_hash,
-                uint64_t* out_nonce) {
-  Runtime& R = rt();
-  std::lock_guard<std::mutex> g(R.mu);
+// One scan with R.mu held by the caller (p1hip_scan; p1hip_scan_batch for the
+// requests it runs individually).
+int scan_held(Runtime& R, const uint8_t* msg, size_t msg_len, uint64_t lower, uint64_t upper, uint64_t* out_hash,
+              uint64_t* out_nonce) {
   const auto t0 = std::chrono::steady_clock::now();
   int rc = ensure_init(R);
   if (rc) return rc;
@@ -900,9 +956,200 @@ int scan_locked(const uint8_t* msg, size_t msg_len, uint64_t lower, uint64_t upp
   return P1HIP_OK;
 }
 
+int scan_locked(const uint8_t* msg, size_t msg_len, uint64_t lower, uint64_t upper, uint64_t* out_hash,
+                uint64_t* out_nonce) {
+  Runtime& R = rt();
+  std::lock_guard<std::mutex> g(R.mu);
+  return scan_held(R, msg, msg_len, lower, upper, out_hash, out_nonce);
+}
+
+// ----------------------------------------------------------------------------
+// p1hip_scan_batch
+// ----------------------------------------------------------------------------
+int batch_check(const p1hip_request_t* reqs, size_t n) {
+  for (size_t i = 0; i < n; ++i) {
+    if (!reqs[i].msg && reqs[i].msg_len > 0)
+      return fail(P1HIP_ERR_ARGS, "request " + std::to_string(i) + ": msg == NULL with msg_len > 0");
+    if (reqs[i].msg_len > P1HIP_MAX_MSG_LEN)
+      return fail(P1HIP_ERR_ARGS, "request " + std::to_string(i) + ": msg_len exceeds P1HIP_MAX_MSG_LEN");
+  }
+  return P1HIP_OK;
+}
+
+std::vector<BatchReq> batch_reqs(const p1hip_request_t* reqs, size_t n) {
+  std::vector<BatchReq> q(n);
+  for (size_t i = 0; i < n; ++i) q[i] = {reqs[i].msg, reqs[i].msg_len, reqs[i].lower, reqs[i].upper};
+  return q;
+}
+
+// Room on device d for a launch pair of `nseg` segments, `nreq` requests and
+// `tiles` tiles.  Called only while the stream is idle (every round of
+// scan_batch_locked ends with a synchronisation).
+int batch_reserve(Dev& d, size_t nseg, size_t nreq, size_t tiles) {
+  auto grown = [](size_t need, size_t floor) {
+    size_t cap = floor;
+    while (cap < need) cap <<= 1;
+    return cap;
+  };
+  if (nseg > d.bseg_cap) {
+    if (d.d_bseg) HIPCHK(hipFree(d.d_bseg));
+    d.d_bseg = nullptr;
+    if (d.h_bseg) HIPCHK(hipHostFree(d.h_bseg));
+    d.h_bseg = nullptr;
+    d.bseg_cap = 0;
+    const size_t cap = grown(nseg, 64);
+    HIPCHK(hipMalloc(&d.d_bseg, cap * sizeof(BatchSeg)));
+    HIPCHK(hipHostMalloc(&d.h_bseg, cap * sizeof(BatchSeg), hipHostMallocDefault));
+    d.bseg_cap = cap;
+  }
+  if (nreq > d.breq_cap) {
+    if (d.d_btile0) HIPCHK(hipFree(d.d_btile0));
+    d.d_btile0 = nullptr;
+    if (d.h_btile0) HIPCHK(hipHostFree(d.h_btile0));
+    d.h_btile0 = nullptr;
+    if (d.d_bout) HIPCHK(hipFree(d.d_bout));
+    d.d_bout = nullptr;
+    if (d.h_bout) HIPCHK(hipHostFree(d.h_bout));
+    d.h_bout = nullptr;
+    d.breq_cap = 0;
+    const size_t cap = grown(nreq, 64);
+    HIPCHK(hipMalloc(&d.d_btile0, (cap + 1) * sizeof(uint32_t)));
+    HIPCHK(hipHostMalloc(&d.h_btile0, (cap + 1) * sizeof(uint32_t), hipHostMallocDefault));
+    HIPCHK(hipMalloc(&d.d_bout, cap * sizeof(Key)));
+    HIPCHK(hipHostMalloc(&d.h_bout, cap * sizeof(Key), hipHostMallocDefault));
+    d.breq_cap = cap;
+  }
+  if (tiles > d.bpart_cap) {
+    if (d.d_bpart) HIPCHK(hipFree(d.d_bpart));
+    d.d_bpart = nullptr;
+    d.bpart_cap = 0;
+    const size_t cap = grown(tiles, 1024);
+    HIPCHK(hipMalloc(&d.d_bpart, cap * sizeof(Key)));
+    d.bpart_cap = cap;
+  }
+  return P1HIP_OK;
+}
+
+int scan_batch_locked(const p1hip_request_t* reqs, size_t n, p1hip_result_t* out) {
+  Runtime& R = rt();
+  std::lock_guard<std::mutex> g(R.mu);
+  const auto t0 = std::chrono::steady_clock::now();
+  int rc = ensure_init(R);
+  if (rc) return rc;
+  const std::vector<BatchReq> q = batch_reqs(reqs, n);
+  const BatchLayout Y = batch_layout(q.data(), n, (int)R.devs.size(), batch_nonce_limit(), batch_tile_limit());
+  // results are gathered here and copied to `out` only when the whole call
+  // has succeeded
+  std::vector<p1hip_result_t> res(n, p1hip_result_t{~0ull, 0});
+  // Coalesced requests, in rounds: round k enqueues launch pair k of every
+  // device that has one (tables, k_batch_scan, k_batch_reduce, copy back, all
+  // on the device's stream) and only then synchronises those streams: one
+  // synchronisation per launch pair, and the devices run side by side.
+  uint64_t tiles = 0, nonces = 0;
+  auto run = [&]() -> int {
+    BatchTable T;
+    std::vector<const BatchLaunch*> round;
+    for (int k = 0;; ++k) {
+      round.clear();
+      for (const BatchLaunch& L : Y.launches)
+        if (L.launch == k) round.push_back(&L);
+      if (round.empty()) break;
+      for (const BatchLaunch* L : round) {
+        Dev& d = R.devs[(size_t)L->device];
+        std::string err = batch_build_table(q.data(), *L, T);
+        if (!err.empty()) return fail(P1HIP_ERR_ARGS, err);
+        const size_t nseg = T.segs.size(), nreq = L->reqs.size();
+        HIPCHK(hipSetDevice(d.ordinal));
+        if ((rc = batch_reserve(d, nseg, nreq, L->tiles)) != P1HIP_OK) return rc;
+        memcpy(d.h_bseg, T.segs.data(), nseg * sizeof(BatchSeg));
+        memcpy(d.h_btile0, T.req_tile0.data(), (nreq + 1) * sizeof(uint32_t));
+        HIPCHK(hipMemcpyAsync(d.d_bseg, d.h_bseg, nseg * sizeof(BatchSeg), hipMemcpyHostToDevice, d.stream));
+        HIPCHK(hipMemcpyAsync(d.d_btile0, d.h_btile0, (nreq + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, d.stream));
+        HIPCHK(launch(d.f_bscan, L->tiles, kBlock, d.stream, (const BatchSeg*)d.d_bseg, (uint32_t)nseg, d.d_bpart));
+        HIPCHK(launch(d.f_breduce, (uint32_t)nreq, kBlock, d.stream, (const Key*)d.d_bpart,
+                      (const uint32_t*)d.d_btile0, d.d_bout));
+        HIPCHK(hipMemcpyAsync(d.h_bout, d.d_bout, nreq * sizeof(Key), hipMemcpyDeviceToHost, d.stream));
+        tiles += L->tiles;
+        nonces += T.nonces;
+      }
+      for (const BatchLaunch* L : round) {
+        Dev& d = R.devs[(size_t)L->device];
+        HIPCHK(hipStreamSynchronize(d.stream));
+        for (size_t r = 0; r < L->reqs.size(); ++r) {
+          const Key kq = finish_key(d.h_bout[r]);
+          res[L->reqs[r]] = p1hip_result_t{kq.h, kq.n};
+        }
+      }
+    }
+    // Larger requests: one by one through the multi-device scan path.
+    if (Y.individual)
+      for (size_t i = 0; i < n; ++i)
+        if (q[i].lower <= q[i].upper && Y.tiles[i] == 0) {
+          rc = scan_held(R, q[i].msg, q[i].len, q[i].lower, q[i].upper, &res[i].hash, &res[i].nonce);
+          if (rc) return fail(rc, "request " + std::to_string(i) + ": " + g_err);
+        }
+    return P1HIP_OK;
+  };
+  if ((rc = run()) != P1HIP_OK) {
+    // leave no launch pair in flight behind a failed call: the next call
+    // rewrites the pinned staging tables
+    const std::string keep = g_err;
+    for (Dev& d : R.devs) (void)hipStreamSynchronize(d.stream);
+    g_err = keep;
+    return rc;
+  }
+  for (size_t i = 0; i < n; ++i) out[i] = res[i];
+  R.bstats.calls++;
+  R.bstats.requests += n;
+  R.bstats.coalesced += Y.coalesced;
+  R.bstats.individual += Y.individual;
+  R.bstats.empty += Y.empty;
+  R.bstats.launches += Y.launches.size();
+  R.bstats.tiles += tiles;
+  R.bstats.nonces += nonces;
+  R.bstats.wall_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return P1HIP_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int p1hip_scan_batch(const p1hip_request_t* reqs, size_t n, p1hip_result_t* out) {
+  if (n == 0) return P1HIP_OK;
+  if (!reqs || !out) return fail(P1HIP_ERR_ARGS, "null request or result array");
+  return guarded([&]() {
+    const int rc = batch_check(reqs, n);
+    return rc ? rc : scan_batch_locked(reqs, n, out);
+  });
+}
+
+int p1hip_batch_layout(const p1hip_request_t* reqs, size_t n, int ndev, uint32_t* tiles, int32_t* device,
+                       int32_t* launch) {
+  if (ndev <= 0) return fail(P1HIP_ERR_ARGS, "ndev <= 0");
+  if (n == 0) return P1HIP_OK;
+  if (!reqs || !tiles || !device || !launch) return fail(P1HIP_ERR_ARGS, "null request or output array");
+  return guarded([&]() {
+    const int rc = batch_check(reqs, n);
+    if (rc) return rc;
+    const std::vector<BatchReq> q = batch_reqs(reqs, n);
+    const BatchLayout Y = batch_layout(q.data(), n, ndev, batch_nonce_limit(), batch_tile_limit());
+    for (size_t i = 0; i < n; ++i) {
+      tiles[i] = Y.tiles[i];
+      device[i] = Y.device[i];
+      launch[i] = Y.launch[i];
+    }
+    return P1HIP_OK;
+  });
+}
+
+int p1hip_get_batch_stats(p1hip_batch_stats_t* out) {
+  if (!out) return fail(P1HIP_ERR_ARGS, "null stats pointer");
+  Runtime& R = rt();
+  std::lock_guard<std::mutex> g(R.mu);
+  *out = R.bstats;
+  return P1HIP_OK;
+}
 
 int p1hip_plan_shards(const uint8_t* msg, size_t msg_len, uint64_t lower, uint64_t upper, int n,
                       uint64_t* first, uint64_t* last) {
@@ -996,6 +1243,7 @@ void p1hip_reset_stats(void) {
   Runtime& R = rt();
   std::lock_guard<std::mutex> g(R.mu);
   R.stats = p1hip_stats_t{};
+  R.bstats = p1hip_batch_stats_t{};
   for (Dev& d : R.devs) {
     d.acc = p1hip_device_stats_t{};
     d.acc.shard_first = 1;  // empty until the next scan
@@ -1034,7 +1282,7 @@ int p1hip_abi_version(void) { return P1HIP_ABI_VERSION; }
 
 const char* p1hip_last_error(void) { return g_err.c_str(); }
 
-const char* p1hip_version(void) { return "p1hip 0.5 gfx950"; }
+const char* p1hip_version(void) { return "p1hip 0.6 gfx950"; }
 
 const char* p1hip_test_knobs(void) {
   static thread_local std::string s;

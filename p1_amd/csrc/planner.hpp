@@ -45,7 +45,15 @@ constexpr uint64_t kMinFastThreads = 1ull << 18;
 #endif
 constexpr int kMaxTabDigits = P1_MAX_TAB_DIGITS;
 
+// 10^e (mod 2^64 past e = 19).  A table: p1hip_scan_batch plans thousands of
+// requests per call, each asking for every decade's bounds.
 inline uint64_t pow10u(int e) {
+  static constexpr uint64_t kPow10[20] = {1ull, 10ull, 100ull, 1000ull, 10000ull, 100000ull, 1000000ull, 10000000ull,
+                                          100000000ull, 1000000000ull, 10000000000ull, 100000000000ull,
+                                          1000000000000ull, 10000000000000ull, 100000000000000ull,
+                                          1000000000000000ull, 10000000000000000ull, 100000000000000000ull,
+                                          1000000000000000000ull, 10000000000000000000ull};
+  if (e >= 0 && e < 20) return kPow10[e];
   uint64_t v = 1;
   for (int i = 0; i < e; ++i) v *= 10u;
   return v;

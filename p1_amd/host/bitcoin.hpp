@@ -19,6 +19,7 @@
 
 #include <stdexcept>
 #include <string>
+#include <vector>
 
 namespace bitcoin {
 
@@ -71,5 +72,11 @@ void ScanChunked(const std::string& msg, uint64_t lower, uint64_t upper, uint64_
 
 // miner.go:55-66 for one decoded Request: returns NewResult(min, minIndex).
 bitcoin::Message HandleRequest(const bitcoin::Message& req, uint64_t chunk = kDefaultChunk);
+
+// The same for many decoded Requests at once: one Result per request, in
+// order, each what HandleRequest returns for it.  Requests of more than
+// `chunk` nonces go through ScanChunked one by one; all others share one
+// p1hip_scan_batch call, which coalesces the small ones into one launch pair.
+std::vector<bitcoin::Message> HandleBatch(const std::vector<bitcoin::Message>& reqs, uint64_t chunk = kDefaultChunk);
 
 }  // namespace miner

@@ -1,8 +1,10 @@
 // miner_gpu.cpp -- the parts of bitcoin.hpp that run on the GPU through
 // libp1hip.so's C ABI: bitcoin::Hash (hash.go:13-17) and the miner's scan
 // step with miner-side chunking (miner.go:55-66).  Every hash is computed by
-// the library; there is no CPU path.
+// the library; there is no CPU path.  HandleBatch answers many requests
+// through one p1hip_scan_batch call.
 #include <string>
+#include <vector>
 
 #include "../../include/p1hip.h"
 #include "bitcoin.hpp"
@@ -50,6 +52,27 @@ bitcoin::Message HandleRequest(const bitcoin::Message& req, uint64_t chunk) {
   uint64_t h = 0, n = 0;
   ScanChunked(req.Data, req.Lower, req.Upper, chunk, &h, &n);
   return bitcoin::NewResult(h, n);
+}
+
+std::vector<bitcoin::Message> HandleBatch(const std::vector<bitcoin::Message>& reqs, uint64_t chunk) {
+  if (chunk == 0) chunk = kDefaultChunk;
+  std::vector<bitcoin::Message> res(reqs.size());
+  std::vector<p1hip_request_t> q;
+  std::vector<size_t> idx;
+  for (size_t i = 0; i < reqs.size(); ++i) {
+    const bitcoin::Message& m = reqs[i];
+    if (m.Lower <= m.Upper && m.Upper - m.Lower >= chunk) {  // more than `chunk` nonces
+      res[i] = HandleRequest(m, chunk);
+    } else {
+      q.push_back({reinterpret_cast<const uint8_t*>(m.Data.data()), m.Data.size(), m.Lower, m.Upper});
+      idx.push_back(i);
+    }
+  }
+  std::vector<p1hip_result_t> out(q.size());
+  const int rc = p1hip_scan_batch(q.data(), q.size(), out.data());
+  if (rc != P1HIP_OK) throw bitcoin::HipError(rc, std::string("p1hip_scan_batch: ") + p1hip_last_error());
+  for (size_t j = 0; j < idx.size(); ++j) res[idx[j]] = bitcoin::NewResult(out[j].hash, out[j].nonce);
+  return res;
 }
 
 }  // namespace miner

@@ -14,11 +14,16 @@
 //   p1miner scan <msg> <lower> <upper>   prints "Result <hash> <nonce>"
 //                                        (the client's output, client.go:59-61)
 //   p1miner hash <msg> <nonce>           prints bitcoin.Hash(msg, nonce)
-//   p1miner serve [--device N] [--chunk C]
+//   p1miner serve [--device N] [--chunk C] [--batch B]
 //                                        one JSON Message per stdin line; every
 //                                        line is answered with one JSON Result
 //                                        line (miner.go:49-67 scans whatever it
-//                                        decoded, as Go's Unmarshal leaves it)
+//                                        decoded, as Go's Unmarshal leaves it).
+//                                        --batch B (B > 1): request lines are
+//                                        collected and answered together, in
+//                                        order, through one p1hip_scan_batch
+//                                        call, on the B-th line, on an empty
+//                                        line (itself not answered) or at EOF
 //   p1miner json                         re-marshals stdin JSON lines (no GPU;
 //                                        wire-format tests): "ERROR" for a
 //                                        syntax error, "TYPEERROR\t" before
@@ -39,6 +44,7 @@
 #include <iostream>
 #include <memory>
 #include <string>
+#include <vector>
 
 #include "../../include/p1hip.h"
 #include "bitcoin.hpp"
@@ -50,7 +56,7 @@
 static int usage() {
   fprintf(stderr,
           "usage: p1miner scan <msg> <lower> <upper> | hash <msg> <nonce> | "
-          "serve [--device N] [--chunk C] | lsp <host:port> [--device N] [--chunk C] [--epoch-limit K] "
+          "serve [--device N] [--chunk C] [--batch B] | lsp <host:port> [--device N] [--chunk C] [--epoch-limit K] "
           "[--epoch-millis M] [--window W] [--copies K] [--connect-copies K] | json | lsp-json | lsp-wrap <connID> <seq> | lsp-unwrap\n");
   return 2;
 }
@@ -183,15 +189,39 @@ int main(int argc, char** argv) {
     }
     if (cmd == "serve") {
       int dev = -1;
-      uint64_t chunk = miner::kDefaultChunk;
+      uint64_t chunk = miner::kDefaultChunk, batch = 1;
       for (int i = 2; i < argc; ++i) {
         if (!strcmp(argv[i], "--device") && i + 1 < argc) dev = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--chunk") && i + 1 < argc) { if (!parse_u64(argv[++i], &chunk)) return usage(); }
+        else if (!strcmp(argv[i], "--batch") && i + 1 < argc) { if (!parse_u64(argv[++i], &batch) || batch == 0) return usage(); }
         else return usage();
       }
       int rc = dev >= 0 ? p1hip_init_devices(&dev, 1) : p1hip_init(0, nullptr);
       if (rc != P1HIP_OK) { fprintf(stderr, "p1hip init: %s\n", p1hip_last_error()); return 1; }
       std::string line;
+      if (batch > 1) {
+        // the same decode per line as below; the answers of a batch are
+        // written together, one Result line per request line, in order
+        std::vector<bitcoin::Message> reqs;
+        auto flush = [&]() {
+          for (const bitcoin::Message& res : miner::HandleBatch(reqs, chunk)) printf("%s\n", bitcoin::Marshal(res).c_str());
+          fflush(stdout);
+          reqs.clear();
+        };
+        while (std::getline(std::cin, line)) {
+          if (line.empty()) {  // flush now; the empty line itself is not answered
+            if (!reqs.empty()) flush();
+            continue;
+          }
+          bitcoin::Message req;
+          bitcoin::Unmarshal(line, &req);
+          reqs.push_back(req);
+          if (reqs.size() >= batch) flush();
+        }
+        if (!reqs.empty()) flush();
+        p1hip_shutdown();
+        return 0;
+      }
       while (std::getline(std::cin, line)) {
         // miner.go:54-55 decodes into a fresh Message and ignores the error,
         // then scans [Lower, Upper] whatever the Type: a line with a type

@@ -5,8 +5,9 @@
 #
 # Builds `make sanitize` (ASan+UBSan and TSan builds of the LSP stack, the
 # server, the client, the CPU test-double miner and the scheduler unit test)
-# and, when present, build/san/asan/p1emu (`make sanitize-emu`, ~6 min: the
-# planner + every kernel variant replayed on the host).  Then re-runs the
+# and, when present, build/san/asan/p1emu and build/san/asan/batch_emu
+# (`make sanitize-emu`, ~6 min: the planner + every kernel variant, and a
+# p1hip_scan_batch call, replayed on the host).  Then re-runs the
 # CPU tests that drive those programs with P1_SAN_DIR pointing at each build
 # (tests/conftest.py host_bin) and every sanitizer writing its reports to
 # files: a run passes only if pytest passes AND no report file appears (a
@@ -26,6 +27,9 @@ for san in asan tsan; do
   tests="tests/test_lsp.py tests/test_lsp_bitcoin.py tests/test_server.py"
   if [ "$san" = asan ] && [ -x build/san/asan/p1emu ]; then
     tests="$tests tests/test_host_logic.py"
+  fi
+  if [ "$san" = asan ] && [ -x build/san/asan/batch_emu ]; then
+    tests="$tests tests/test_batch_host.py"
   fi
   t0=$(date +%s)
   python3 -m pytest $tests -q -m "not gpu" -n 4 -p no:cacheprovider > "$logs/pytest.txt" 2>&1
