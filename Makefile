@@ -5,9 +5,9 @@ HIPFLAGS ?= -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -Wall
 LLVM ?= /opt/rocm/lib/llvm/bin
 CSRC := p1_amd/csrc
 HDRS := $(CSRC)/sha256_dev.hpp $(CSRC)/scan_core.hpp $(CSRC)/planner.hpp $(CSRC)/fast_variants.inc $(CSRC)/variant_cost.inc \
-        $(CSRC)/scan_abi.hpp $(CSRC)/batch_abi.hpp $(CSRC)/batch_plan.hpp include/p1hip.h
+        $(CSRC)/scan_abi.hpp $(CSRC)/scan_pack.hpp $(CSRC)/argmin_dev.hpp $(CSRC)/batch_abi.hpp $(CSRC)/batch_plan.hpp include/p1hip.h
 # what the device code includes (the host-side planner does not rebuild it)
-DEVHDRS := $(CSRC)/sha256_dev.hpp $(CSRC)/scan_core.hpp $(CSRC)/fast_variants.inc $(CSRC)/scan_abi.hpp
+DEVHDRS := $(CSRC)/sha256_dev.hpp $(CSRC)/scan_core.hpp $(CSRC)/fast_variants.inc $(CSRC)/scan_abi.hpp $(CSRC)/argmin_dev.hpp
 # device code: HIP C++ -> gfx950 assembly -> tools/isa_post.py post-pass
 # (ISAPOST: LLVM's own encodings kept (--no-e64); loop labels aligned; every
 # loop body's straight-line segments reordered into runs of one issue class
@@ -55,7 +55,7 @@ $(BUILD)/p1hip_kernels_blob.o: $(CSRC)/p1hip_kernels_blob.S $(BUILD)/p1hip_kerne
 # the generic per-thread path, so no post-pass and a compile of seconds.  Its
 # blob is linked AFTER the scan object's: the scan object stays the first
 # AMDGPU ELF in libp1hip.so (tests/test_codeobj.py).
-BATCHDEVHDRS := $(CSRC)/sha256_dev.hpp $(CSRC)/scan_core.hpp $(CSRC)/scan_abi.hpp $(CSRC)/batch_abi.hpp
+BATCHDEVHDRS := $(CSRC)/sha256_dev.hpp $(CSRC)/scan_core.hpp $(CSRC)/scan_abi.hpp $(CSRC)/batch_abi.hpp $(CSRC)/argmin_dev.hpp
 BATCHDEVFLAGS ?= -O3 -std=c++17 --offload-arch=$(ARCH) --cuda-device-only -Wall
 .SECONDARY: $(BUILD)/p1hip_batch.s $(BUILD)/p1hip_batch.o
 $(BUILD)/p1hip_batch.s: $(CSRC)/p1hip_batch_kernels.hip $(BATCHDEVHDRS)
@@ -127,7 +127,8 @@ tools/xcd_probe: tools/xcd_probe.hip
 tools/vbank: tools/vbank.hip
 	$(HIPCC) --offload-arch=gfx950 -O2 -std=c++17 -o $@ tools/vbank.hip
 
-# host-only replay of the kernels' per-thread code (layout tests; not product)
+# host-only replay of the kernels' per-thread code and of the library's launch
+# packing (layout and segment-table tests; not product)
 tools/p1emu: tools/p1emu.cpp $(HDRS)
 	$(HIPCC) -O2 -std=c++17 -DP1_NV2_PLAIN -o $@ tools/p1emu.cpp
 

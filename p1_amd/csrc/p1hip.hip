@@ -5,10 +5,12 @@
 // miner/miner.go:56-63 (see include/p1hip.h for the exact contract).
 //
 // Device pipeline of one p1hip_scan on one device (one HIP stream):
-//   planner.hpp  -> list of pieces (fast: one thread per 10^k nonces;
-//                   generic: one thread per nonce, for ragged edges)
-//   k_scan       -> one launch, one segment per piece (p1hip_kernels.hip)
-//   k_reduce     -> one workgroup folds all partials into the device result
+//   planner.hpp   -> list of pieces (fast: one thread per 10^k nonces;
+//                    generic: one thread per nonce, for ragged edges)
+//   scan_pack.hpp -> the pieces ordered and cut into launches, one segment
+//                    table per launch (host only; tools/p1emu replays it)
+//   k_scan        -> one launch, one segment per piece (p1hip_kernels.hip)
+//   k_reduce      -> one workgroup folds all partials into the device result
 // The kernels live in a gfx950 code object built from p1hip_kernels.hip via
 // assembly + tools/isa_post.py (Makefile) and embedded in this library
 // (p1hip_kernels_blob.S); each device loads it with hipModuleLoadData.
@@ -19,6 +21,10 @@
 // per device, k_batch_scan + k_batch_reduce, from a second, small code object
 // (p1hip_batch_kernels.hip, p1hip_batch_blob.S); layout and tables come from
 // batch_plan.hpp, which tools/batch_emu shares.
+//
+// Order of this file: runtime state, helpers, the scan path, the batch path,
+// reduce_pairs, then the C ABI in one extern "C" block.  Every HIP and RCCL
+// call of the library is in this file (tests/test_stream_discipline.py).
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
@@ -32,12 +38,14 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <utility>
 #include <vector>
 
 #include "../../include/p1hip.h"
 #include "batch_plan.hpp"
 #include "planner.hpp"
 #include "scan_abi.hpp"
+#include "scan_pack.hpp"
 
 // the embedded gfx950 code objects (p1hip_kernels_blob.S, p1hip_batch_blob.S)
 extern "C" const unsigned char p1hip_kernels_co[];
@@ -45,19 +53,11 @@ extern "C" const unsigned char p1hip_batch_co[];
 
 using namespace p1;
 
-static bool has_variant(int fv, int mode, bool trail) {
-#define P1_CASE(FV, MODE, TR) \
-  if (fv == FV && mode == MODE && trail == TR) return true;
-#include "fast_variants.inc"
-#undef P1_CASE
-  return false;
-}
-
-// ----------------------------------------------------------------------------
-// Runtime state
-// ----------------------------------------------------------------------------
 namespace {
 
+// ----------------------------------------------------------------------------
+// Errors
+// ----------------------------------------------------------------------------
 thread_local std::string g_err;
 
 int fail(int rc, const std::string& what) {
@@ -93,109 +93,175 @@ int guarded(Fn&& fn) {
       return fail(P1HIP_ERR_RCCL, std::string(#expr) + ": " + ncclGetErrorString(r_));      \
   } while (0)
 
-constexpr uint32_t kMaxSegs = 64;              // segments per launch
-// Workgroups per launch: 2^22 x 256 threads stays below HIP's 2^32-thread
-// grid limit and keeps configs[3] on one GPU (2^38 nonces, ~1.07M
-// workgroups) in one launch, i.e. one grid drain per scan.
-constexpr uint32_t kMaxLaunchBlocks = 1u << 22;
+// ----------------------------------------------------------------------------
+// Limits and test knobs
+// ----------------------------------------------------------------------------
+// Device copies of MODE 5 K+W tables are cached, at most this many ...
+constexpr size_t kMaxKwTabs = 8;
+// ... and at most this many bytes of them (a 7-digit table is 2.56 GB; one
+// scan needs at most one table per MODE 5 decade, < 2.9 GB in all)
+constexpr uint64_t kMaxKwTabBytes = 8ull << 30;
+// A device's share runs in pieces of at most this many nonces (run_share).
+constexpr uint64_t kMaxScanSpan = 1ull << 40;
 
-// P1HIP_SMALL_MAX_NONCES (tests only, read per scan): ranges of at most this
-// many nonces take the one-launch small path (default kSmallMaxNonces; 0
-// turns it off so small parity ranges exercise the fast kernel variants).
-// Every P1HIP_* test knob is read through test_knob(): it is honoured only
-// while the master switch P1HIP_TEST_KNOBS=1 is set (the test fixtures set
-// it), so a stray knob in a production miner's environment changes nothing.
-// p1hip_test_knobs() lists the knobs in force, for bench.py to refuse.
-const char* const kTestKnobs[] = {
-    "P1HIP_SMALL_MAX_NONCES", "P1HIP_MAX_LAUNCH_BLOCKS", "P1HIP_MAX_SCAN_SPAN", "P1HIP_KWTAB_MAX_BYTES",
-    "P1HIP_NO_RCCL",          "P1HIP_FORCE_RCCL",        "P1HIP_MIN_FAST_THREADS", "P1HIP_TEST_FAIL_DEVICE",
-    "P1HIP_NO_TABLE",         "P1HIP_NO_SPLIT",          "P1HIP_SCAN_GRID",        "P1HIP_BATCH_MAX_NONCES",
-    "P1HIP_BATCH_MAX_TILES",
+// Every P1HIP_* test knob, in the order p1hip_test_knobs() lists them.  A knob
+// is honoured only while the master switch P1HIP_TEST_KNOBS=1 is set (the
+// test fixtures set it), so a stray knob in a production miner's environment
+// changes nothing; bench.py refuses to time with any in force.  All are read
+// through knob(): unset or empty gives `def`; a kFlag is on when its value
+// starts with '1'; a number above `max` becomes `max`; 0 is a real 0 for
+// kValue and means `def` for kZeroDef.
+enum KnobKind { kValue, kZeroDef, kFlag };
+enum KnobWhen { kPerScan, kPerBatch, kAtInit };  // init: the open devices keep what they were opened with
+enum KnobId {
+  kSmallMaxNoncesKnob, kMaxLaunchBlocksKnob, kMaxScanSpanKnob, kKwtabMaxBytesKnob, kNoRcclKnob, kForceRcclKnob,
+  kMinFastThreadsKnob, kTestFailDeviceKnob, kNoTableKnob, kNoSplitKnob, kScanGridKnob, kBatchMaxNoncesKnob,
+  kBatchMaxTilesKnob, kKnobCount
 };
+struct Knob {
+  const char* name;
+  uint64_t def, max;
+  KnobKind kind;
+  KnobWhen when;
+  const char* what;
+};
+const Knob kKnobs[] = {
+    {"P1HIP_SMALL_MAX_NONCES", kSmallMaxNonces, kSmallMaxNonces, kValue, kPerScan,
+     "shares of at most this many nonces take the one-launch small path; 0 turns it off, so small parity ranges "
+     "run the fast kernel variants"},
+    {"P1HIP_MAX_LAUNCH_BLOCKS", kMaxLaunchBlocks, kMaxLaunchBlocks, kZeroDef, kPerScan,
+     "workgroups per k_scan launch, so GPU tests run the multi-launch path on small ranges; a larger piece gets "
+     "a launch of its own (at most kMaxFastThreads / kBlock = 2^18 workgroups, far below HIP's grid limit)"},
+    {"P1HIP_MAX_SCAN_SPAN", kMaxScanSpan, ~0ull, kZeroDef, kPerScan, "nonces per piece of a device's share"},
+    {"P1HIP_KWTAB_MAX_BYTES", kMaxKwTabBytes, ~0ull, kValue, kPerScan,
+     "MODE 5 table cap; a larger table re-plans the share without MODE 5"},
+    {"P1HIP_NO_RCCL", 0, 1, kFlag, kAtInit,
+     "combine the per-device results through the host, so the multi-device path (threads, sharding, combine) "
+     "runs with the same GPU listed twice on a 1-GPU box"},
+    {"P1HIP_FORCE_RCCL", 0, 1, kFlag, kAtInit, "a communicator even for one device"},
+    {"P1HIP_MIN_FAST_THREADS", kMinFastThreads, ~0ull, kValue, kAtInit,
+     "planner occupancy floor; 1 keeps k = 3 on small ranges so every k = 3 variant runs on the GPU"},
+    {"P1HIP_TEST_FAIL_DEVICE", ~0ull, ~0ull, kValue, kAtInit,
+     "device index whose scan phase reports a failure (the multi-device error path); default -1: none"},
+    {"P1HIP_NO_TABLE", 0, 1, kFlag, kAtInit,
+     "no MODE 5: layouts whose tail block 1 holds only lo digits run the digit-update variants (A/B, and a "
+     "second kernel path to cross-check MODE 5)"},
+    {"P1HIP_NO_SPLIT", 0, 1, kFlag, kAtInit,
+     "straddling lo digits use mode 2 instead of the split modes (A/B builds with -DP1_NV2_PLAIN)"},
+    {"P1HIP_SCAN_GRID", 0, kMaxLaunchBlocks, kZeroDef, kPerScan,
+     "k_scan's grid instead of the device's workgroup slots (the default, 0); at or above a launch's tile count "
+     "every workgroup runs one tile and the queue hands out none (the round-5 dispatch, same code object)"},
+    {"P1HIP_BATCH_MAX_NONCES", kBatchMaxNonces, kBatchMaxNonces, kValue, kPerBatch,
+     "requests of at most this many nonces are coalesced by p1hip_scan_batch; 0 runs every request "
+     "individually; independent of P1HIP_SMALL_MAX_NONCES"},
+    {"P1HIP_BATCH_MAX_TILES", kBatchMaxTiles, kBatchMaxTiles, kZeroDef, kPerBatch,
+     "tiles per launch pair, so GPU tests run several launch pairs on small batches (batch_layout raises it to "
+     "the largest single request's tile count)"},
+};
+static_assert(sizeof kKnobs / sizeof kKnobs[0] == kKnobCount, "one row per KnobId, in its order");
 
 bool test_knobs_on() {
   const char* m = getenv("P1HIP_TEST_KNOBS");
   return m && m[0] == '1' && m[1] == 0;
 }
 
+// the knob's text if it is in force, else null
 const char* test_knob(const char* name) {
   if (!test_knobs_on()) return nullptr;
   const char* v = getenv(name);
   return v && *v ? v : nullptr;
 }
 
-uint64_t small_limit() {
-  const char* v = test_knob("P1HIP_SMALL_MAX_NONCES");
-  if (!v || !*v) return kSmallMaxNonces;
+uint64_t knob(KnobId id) {
+  const Knob& K = kKnobs[id];
+  const char* v = test_knob(K.name);
+  if (!v) return K.def;
+  if (K.kind == kFlag) return v[0] == '1';
   const uint64_t n = strtoull(v, nullptr, 10);
-  return n < kSmallMaxNonces ? n : kSmallMaxNonces;
+  if (n == 0 && K.kind == kZeroDef) return K.def;
+  return n < K.max ? n : K.max;
 }
 
-// P1HIP_MAX_LAUNCH_BLOCKS (tests only, read per scan): a lower per-launch
-// workgroup cap, so GPU tests run the multi-launch path on small ranges.  A
-// piece larger than the cap gets a launch of its own (a piece is at most
-// kMaxFastThreads / kBlock = 2^18 workgroups, far below HIP's grid limit).
-uint64_t launch_block_limit() {
-  const char* v = test_knob("P1HIP_MAX_LAUNCH_BLOCKS");
-  const uint64_t n = v && *v ? strtoull(v, nullptr, 10) : 0;
-  if (n == 0 || n >= kMaxLaunchBlocks) return kMaxLaunchBlocks;
-  return n;
-}
+// ----------------------------------------------------------------------------
+// Runtime state
+// ----------------------------------------------------------------------------
+// A device (hipMalloc) or pinned host (hipHostMalloc) array that grows by
+// powers of two and is kept.  It frees what it holds when it is destroyed or
+// assigned over, so whoever does that has the owning device current and its
+// stream synchronised (dev_release; reduce_pairs_locked's locals).
+template <typename T, bool kPinned>
+struct Buf {
+  T* p = nullptr;
+  size_t cap = 0;  // elements `reserve` promised (`extra` more are allocated)
 
-// P1HIP_BATCH_MAX_NONCES (tests only, read per batch call): requests of at
-// most this many nonces are coalesced by p1hip_scan_batch (default and cap
-// kBatchMaxNonces; 0 runs every request individually).  It does not depend on
-// P1HIP_SMALL_MAX_NONCES.
-uint64_t batch_nonce_limit() {
-  const char* v = test_knob("P1HIP_BATCH_MAX_NONCES");
-  if (!v) return kBatchMaxNonces;
-  const uint64_t n = strtoull(v, nullptr, 10);
-  return n < kBatchMaxNonces ? n : kBatchMaxNonces;
-}
+  Buf() = default;
+  Buf(const Buf&) = delete;
+  Buf(Buf&& o) noexcept : p(std::exchange(o.p, nullptr)), cap(std::exchange(o.cap, 0)) {}
+  Buf& operator=(Buf&& o) noexcept {
+    if (this != &o) {
+      (void)release();
+      p = std::exchange(o.p, nullptr);
+      cap = std::exchange(o.cap, 0);
+    }
+    return *this;
+  }
+  ~Buf() { (void)release(); }
 
-// P1HIP_BATCH_MAX_TILES (tests only, read per batch call): tiles per launch
-// pair, so GPU tests run several launch pairs on small batches (batch_layout
-// raises it to the largest single request's tile count).
-uint64_t batch_tile_limit() {
-  const char* v = test_knob("P1HIP_BATCH_MAX_TILES");
-  const uint64_t n = v ? strtoull(v, nullptr, 10) : 0;
-  if (n == 0 || n >= kBatchMaxTiles) return kBatchMaxTiles;
-  return n;
-}
+  hipError_t release() {
+    hipError_t e = hipSuccess;
+    if (p) e = kPinned ? hipHostFree(p) : hipFree(p);
+    p = nullptr;  // never a dangling pointer with a stale capacity
+    cap = 0;
+    return e;
+  }
+  // Room for `need` elements: if there is less, free, then allocate the next
+  // power-of-two multiple of `floor` at or above `need` (+ `extra`).  Only
+  // while the stream is idle.  On failure the buffer is empty.
+  hipError_t reserve(size_t need, size_t floor, size_t extra = 0) {
+    if (need <= cap) return hipSuccess;
+    hipError_t e = release();
+    if (e != hipSuccess) return e;
+    size_t n = floor;
+    while (n < need) n <<= 1;
+    const size_t bytes = (n + extra) * sizeof(T);
+    e = kPinned ? hipHostMalloc(&p, bytes, hipHostMallocDefault) : hipMalloc(&p, bytes);
+    if (e != hipSuccess) p = nullptr;
+    else cap = n;
+    return e;
+  }
+};
+template <typename T> using DevBuf = Buf<T, false>;
+template <typename T> using PinnedBuf = Buf<T, true>;
 
+// Move-only (its buffers are): fine in std::vector<Dev> and for d = Dev().
 struct Dev {
   int ordinal = -1;
   hipStream_t stream = nullptr;
-  Key* d_part = nullptr;
-  size_t part_cap = 0;
-  Key* d_res = nullptr;         // 1 Key
-  Key* d_gather = nullptr;      // ndev Keys (multi-device)
-  Key* h_res = nullptr;         // pinned, ndev Keys
-  Segment* d_seg = nullptr;     // segment tables, kMaxSegs per launch slot
-  Segment* h_seg = nullptr;     // pinned staging for the tables
-  size_t seg_cap = 0;           // launch slots allocated
+  DevBuf<Key> d_part;           // one partial per tile of a scan
+  DevBuf<Key> d_res;            // 1 Key
+  DevBuf<Key> d_gather;         // ndev Keys (multi-device)
+  PinnedBuf<Key> h_res;         // ndev Keys
+  DevBuf<Segment> d_seg;        // segment tables, kMaxSegs per launch slot
+  PinnedBuf<Segment> h_seg;     // staging for the tables
   ncclComm_t comm = nullptr;
   hipModule_t mod = nullptr;    // embedded code object, loaded on this device
   hipFunction_t f_scan = nullptr, f_reduce = nullptr, f_pairs = nullptr, f_small = nullptr, f_kwtable = nullptr;
-  Key* d_small_part = nullptr;  // kSmallMaxBlocks partials of k_scan_small
-  uint32_t* d_ticket = nullptr; // k_scan_small's last-workgroup counter (0 between scans)
-  uint32_t* d_scan_ticket = nullptr;  // k_scan's work queue: [tiles handed out, workgroups done] (0 between launches)
+  DevBuf<Key> d_small_part;     // kSmallMaxBlocks partials of k_scan_small
+  DevBuf<uint32_t> d_ticket;    // k_scan_small's last-workgroup counter (0 between scans)
+  DevBuf<uint32_t> d_scan_ticket;  // k_scan's work queue: [tiles handed out, workgroups done] (0 between launches)
   uint32_t scan_grid = 0;       // k_scan workgroups the device holds at once (occupancy x CUs)
   bool small_used = false;      // this scan ran k_scan_small (result already in h_res[0])
   // p1hip_scan_batch: its own code object and buffers (grown on demand, kept
   // across calls; no p1hip_scan touches them)
   hipModule_t bmod = nullptr;
   hipFunction_t f_bscan = nullptr, f_breduce = nullptr;
-  BatchSeg* d_bseg = nullptr;   // segment table of one launch pair
-  BatchSeg* h_bseg = nullptr;   // pinned staging
-  size_t bseg_cap = 0;
-  uint32_t* d_btile0 = nullptr; // first tile of each request (+ end)
-  uint32_t* h_btile0 = nullptr; // pinned staging
-  Key* d_bout = nullptr;        // one Key per request
-  Key* h_bout = nullptr;        // pinned
-  size_t breq_cap = 0;          // requests the three above hold
-  Key* d_bpart = nullptr;       // one partial per tile
-  size_t bpart_cap = 0;
+  DevBuf<BatchSeg> d_bseg;      // segment table of one launch pair
+  PinnedBuf<BatchSeg> h_bseg;   // staging
+  DevBuf<uint32_t> d_btile0;    // first tile of each request (+ end)
+  PinnedBuf<uint32_t> h_btile0; // staging
+  DevBuf<Key> d_bout;           // one Key per request
+  PinnedBuf<Key> h_bout;
+  DevBuf<Key> d_bpart;          // one partial per tile
   std::vector<hipEvent_t> evs;  // profiling event pool (pairs)
   // MODE 5 K+W tables on this device, least recently used first (built by
   // k_kwtable; keyed by the block-1 template and k)
@@ -207,10 +273,7 @@ struct Dev {
   };
   std::vector<KwTab> kwtabs;
   uint64_t range_id = 0;        // run_range calls on this device
-  // per-scan accounting filled by run_range
-  uint64_t fast_launches = 0, fast_nonces = 0, fast_ops = 0, gen_launches = 0, gen_nonces = 0;
-  uint64_t scan_launches = 0, scan_nonces = 0, scan_ops = 0;
-  double scan_ms = 0.0;
+  ScanCounters ctr;             // per-scan accounting (run_small, run_range, run_share)
   uint64_t replans = 0;         // shares re-planned without MODE 5 (this scan)
   // since p1hip_reset_stats, for p1hip_get_device_stats
   p1hip_device_stats_t acc{};
@@ -220,26 +283,9 @@ struct Runtime {
   std::mutex mu;
   std::vector<Dev> devs;
   bool profiling = false;
+  // the kAtInit knobs, as the open devices were opened with
   bool use_rccl = true;   // multi-device combine through ncclAllGather
-  bool rccl_one = false;  // P1HIP_FORCE_RCCL=1: communicator even for one device
-  // Test-only knobs, read from the environment at init (never set in
-  // production; honoured only under P1HIP_TEST_KNOBS=1, see test_knob):
-  //   P1HIP_MIN_FAST_THREADS  planner occupancy floor (1 keeps k = 3 on small
-  //                           ranges so every k = 3 variant runs on the GPU)
-  //   P1HIP_TEST_FAIL_DEVICE  device index whose scan phase reports a failure
-  //                           (exercises the multi-device error path)
-  //   P1HIP_MAX_LAUNCH_BLOCKS workgroups per k_scan launch (read per scan,
-  //                           launch_block_limit)
-  //   P1HIP_MAX_SCAN_SPAN     nonces per piece of a device's share (run_share)
-  //   P1HIP_KWTAB_MAX_BYTES   MODE 5 table cap (read per scan; a larger table
-  //                           re-plans the share without MODE 5)
-  //   P1HIP_NO_TABLE          no MODE 5: layouts whose tail block 1 holds only
-  //                           lo digits run the digit-update variants (A/B,
-  //                           and a second kernel path to cross-check MODE 5)
-  //   P1HIP_NO_SPLIT          straddling lo digits use mode 2 instead of the
-  //                           split modes (A/B builds with -DP1_NV2_PLAIN)
-  //   P1HIP_SCAN_GRID         k_scan's grid (read per scan, scan_grid_for;
-  //                           large = one tile per workgroup, no queue)
+  bool rccl_one = false;  // communicator even for one device
   uint64_t min_fast_threads = kMinFastThreads;
   bool split = true;
   bool tabulate = true;
@@ -259,35 +305,87 @@ Runtime& rt() {
   return *r;
 }
 
+// ----------------------------------------------------------------------------
+// Helpers
+// ----------------------------------------------------------------------------
+int device_count(int* count) {
+  *count = 0;
+  if (hipGetDeviceCount(count) != hipSuccess || *count <= 0)
+    return fail(P1HIP_ERR_NO_DEVICE, "no HIP device visible");
+  return P1HIP_OK;
+}
+
+// hipModuleLaunchKernel with the arguments as a pointer array
+template <typename... Args>
+hipError_t launch(hipFunction_t f, uint32_t blocks, uint32_t threads, hipStream_t st, Args... args) {
+  void* params[] = {(void*)&args...};
+  return hipModuleLaunchKernel(f, blocks, 1, 1, threads, 1, 1, 0, st, params, nullptr);
+}
+
+// Profiling: scan launches sit between event pairs from the device's pool.
+// ev_record records event `nev` (growing the pool) and counts it; ev_sum
+// waits for the last one and adds every pair's elapsed time to scan_ms.
+int ev_record(Dev& d, size_t& nev) {
+  if (d.evs.size() <= nev) {
+    hipEvent_t e;
+    HIPCHK(hipEventCreate(&e));
+    d.evs.push_back(e);
+  }
+  HIPCHK(hipEventRecord(d.evs[nev], d.stream));
+  ++nev;
+  return P1HIP_OK;
+}
+
+int ev_sum(Dev& d, size_t nev) {
+  if (!nev) return P1HIP_OK;
+  HIPCHK(hipEventSynchronize(d.evs[nev - 1]));
+  for (size_t i = 0; i + 1 < nev; i += 2) {
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, d.evs[i], d.evs[i + 1]));
+    d.ctr.scan_ms += ms;
+  }
+  return P1HIP_OK;
+}
+
+Key finish_key(Key k) {
+  if (k.h == ~0ull) k.n = 0;  // identity (MaxUint64, 0) of miner.go:56
+  return k;
+}
+
+void add_counters(p1hip_stats_t& s, const ScanCounters& c) {
+  s.fast_launches += c.fast_launches;
+  s.fast_nonces += c.fast_nonces;
+  s.fast_alg_ops += c.fast_ops;
+  s.generic_launches += c.gen_launches;
+  s.generic_nonces += c.gen_nonces;
+  s.scan_launches += c.scan_launches;
+  s.scan_nonces += c.scan_nonces;
+  s.scan_alg_ops += c.scan_ops;
+  s.scan_kernel_ms += c.scan_ms;
+}
+
+void add_counters(p1hip_device_stats_t& a, const ScanCounters& c) {
+  a.scans++;
+  a.scan_launches += c.scan_launches;
+  a.scan_nonces += c.scan_nonces;
+  a.scan_alg_ops += c.scan_ops;
+  a.scan_kernel_ms += c.scan_ms;
+}
+
+// ----------------------------------------------------------------------------
+// Devices: open, close
+// ----------------------------------------------------------------------------
 int dev_release(Dev& d) {
   if (d.ordinal < 0) return 0;
   (void)hipSetDevice(d.ordinal);
   if (d.stream) (void)hipStreamSynchronize(d.stream);
   for (hipEvent_t e : d.evs) (void)hipEventDestroy(e);
-  d.evs.clear();
   for (Dev::KwTab& t : d.kwtabs) (void)hipFree(t.dptr);
-  d.kwtabs.clear();
-  if (d.d_seg) (void)hipFree(d.d_seg);
-  if (d.h_seg) (void)hipHostFree(d.h_seg);
   if (d.comm) ncclCommDestroy(d.comm);
-  if (d.d_part) (void)hipFree(d.d_part);
-  if (d.d_res) (void)hipFree(d.d_res);
-  if (d.d_gather) (void)hipFree(d.d_gather);
-  if (d.d_small_part) (void)hipFree(d.d_small_part);
-  if (d.d_ticket) (void)hipFree(d.d_ticket);
-  if (d.d_scan_ticket) (void)hipFree(d.d_scan_ticket);
-  if (d.d_bseg) (void)hipFree(d.d_bseg);
-  if (d.h_bseg) (void)hipHostFree(d.h_bseg);
-  if (d.d_btile0) (void)hipFree(d.d_btile0);
-  if (d.h_btile0) (void)hipHostFree(d.h_btile0);
-  if (d.d_bout) (void)hipFree(d.d_bout);
-  if (d.h_bout) (void)hipHostFree(d.h_bout);
-  if (d.d_bpart) (void)hipFree(d.d_bpart);
-  if (d.h_res) (void)hipHostFree(d.h_res);
   if (d.stream) (void)hipStreamDestroy(d.stream);
   if (d.mod) (void)hipModuleUnload(d.mod);
   if (d.bmod) (void)hipModuleUnload(d.bmod);
-  d = Dev();
+  d = Dev();  // every Buf frees itself here: this device is current, its work is done
   return 0;
 }
 
@@ -296,7 +394,68 @@ void shutdown_locked(Runtime& R) {
   R.devs.clear();
 }
 
-int init_devs(Runtime& R, const std::vector<int>& ords);
+int init_devs(Runtime& R, const std::vector<int>& ords) {
+  int count = 0;
+  if (int rc = device_count(&count)) return rc;
+  const int nd = (int)ords.size();
+  std::vector<int> cus(ords.size());
+  for (int i = 0; i < nd; ++i) {
+    const int o = ords[i];
+    if (o < 0 || o >= count) return fail(P1HIP_ERR_NO_DEVICE, "device ordinal out of range: " + std::to_string(o));
+    hipDeviceProp_t prop;
+    HIPCHK(hipGetDeviceProperties(&prop, o));
+    if (std::string(prop.gcnArchName).rfind("gfx950", 0) != 0)
+      return fail(P1HIP_ERR_NO_DEVICE, std::string("device is not gfx950: ") + prop.gcnArchName);
+    cus[i] = prop.multiProcessorCount;
+  }
+  R.devs.resize(ords.size());
+  for (int i = 0; i < nd; ++i) {
+    Dev& d = R.devs[i];
+    d.ordinal = ords[i];
+    HIPCHK(hipSetDevice(d.ordinal));
+    HIPCHK(hipStreamCreateWithFlags(&d.stream, hipStreamNonBlocking));
+    HIPCHK(hipModuleLoadData(&d.mod, p1hip_kernels_co));
+    HIPCHK(hipModuleGetFunction(&d.f_scan, d.mod, "k_scan"));
+    HIPCHK(hipModuleGetFunction(&d.f_reduce, d.mod, "k_reduce"));
+    HIPCHK(hipModuleGetFunction(&d.f_pairs, d.mod, "k_pairs"));
+    HIPCHK(hipModuleGetFunction(&d.f_small, d.mod, "k_scan_small"));
+    HIPCHK(hipModuleGetFunction(&d.f_kwtable, d.mod, "k_kwtable"));
+    HIPCHK(hipModuleLoadData(&d.bmod, p1hip_batch_co));
+    HIPCHK(hipModuleGetFunction(&d.f_bscan, d.bmod, "k_batch_scan"));
+    HIPCHK(hipModuleGetFunction(&d.f_breduce, d.bmod, "k_batch_reduce"));
+    // fixed-size buffers: floor = need, so exactly that many elements
+    HIPCHK(d.d_small_part.reserve(kSmallMaxBlocks, kSmallMaxBlocks));
+    HIPCHK(d.d_ticket.reserve(1, 1));
+    HIPCHK(d.d_scan_ticket.reserve(2, 2));
+    // on the library's own stream: a null-stream call would give every
+    // process a second hardware queue (8 miner processes share one GPU)
+    HIPCHK(hipMemsetAsync(d.d_ticket.p, 0, sizeof(uint32_t), d.stream));
+    HIPCHK(hipMemsetAsync(d.d_scan_ticket.p, 0, 2 * sizeof(uint32_t), d.stream));
+    // k_scan's grid: every workgroup slot of the device once (the work queue
+    // hands the tiles out; p1hip_kernels.hip k_scan)
+    int per_cu = 0;
+    HIPCHK(hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, d.f_scan, kBlock, 0));
+    if (per_cu < 1 || cus[i] < 1)
+      return fail(P1HIP_ERR_HIP, "k_scan occupancy: " + std::to_string(per_cu) + " blocks per CU");
+    d.scan_grid = (uint32_t)per_cu * (uint32_t)cus[i];
+    HIPCHK(hipStreamSynchronize(d.stream));
+    HIPCHK(d.d_res.reserve(1, 1));
+    HIPCHK(d.d_gather.reserve((size_t)nd, (size_t)nd));
+    HIPCHK(d.h_res.reserve((size_t)nd, (size_t)nd));
+  }
+  R.use_rccl = !knob(kNoRcclKnob);
+  R.rccl_one = knob(kForceRcclKnob) && R.use_rccl;
+  R.min_fast_threads = knob(kMinFastThreadsKnob);
+  R.split = !knob(kNoSplitKnob);
+  R.tabulate = !knob(kNoTableKnob);
+  R.fail_device = (int)(int64_t)knob(kTestFailDeviceKnob);
+  if ((nd > 1 || R.rccl_one) && R.use_rccl) {
+    std::vector<ncclComm_t> comms(nd);
+    NCCLCHK(ncclCommInitAll(comms.data(), nd, ords.data()));
+    for (int i = 0; i < nd; ++i) R.devs[i].comm = comms[i];
+  }
+  return P1HIP_OK;
+}
 
 int init_locked(Runtime& R, const std::vector<int>& ords) {
   if (!R.devs.empty()) {
@@ -314,154 +473,44 @@ int init_locked(Runtime& R, const std::vector<int>& ords) {
   return rc;
 }
 
-int init_devs(Runtime& R, const std::vector<int>& ords) {
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
-    return fail(P1HIP_ERR_NO_DEVICE, "no HIP device visible");
-  for (int o : ords) {
-    if (o < 0 || o >= count) return fail(P1HIP_ERR_NO_DEVICE, "device ordinal out of range: " + std::to_string(o));
-    hipDeviceProp_t prop;
-    HIPCHK(hipGetDeviceProperties(&prop, o));
-    if (std::string(prop.gcnArchName).rfind("gfx950", 0) != 0)
-      return fail(P1HIP_ERR_NO_DEVICE, std::string("device is not gfx950: ") + prop.gcnArchName);
-  }
-  R.devs.resize(ords.size());
-  const int nd = (int)ords.size();
-  for (int i = 0; i < nd; ++i) {
-    Dev& d = R.devs[i];
-    d.ordinal = ords[i];
-    HIPCHK(hipSetDevice(d.ordinal));
-    HIPCHK(hipStreamCreateWithFlags(&d.stream, hipStreamNonBlocking));
-    HIPCHK(hipModuleLoadData(&d.mod, p1hip_kernels_co));
-    HIPCHK(hipModuleGetFunction(&d.f_scan, d.mod, "k_scan"));
-    HIPCHK(hipModuleGetFunction(&d.f_reduce, d.mod, "k_reduce"));
-    HIPCHK(hipModuleGetFunction(&d.f_pairs, d.mod, "k_pairs"));
-    HIPCHK(hipModuleGetFunction(&d.f_small, d.mod, "k_scan_small"));
-    HIPCHK(hipModuleGetFunction(&d.f_kwtable, d.mod, "k_kwtable"));
-    HIPCHK(hipModuleLoadData(&d.bmod, p1hip_batch_co));
-    HIPCHK(hipModuleGetFunction(&d.f_bscan, d.bmod, "k_batch_scan"));
-    HIPCHK(hipModuleGetFunction(&d.f_breduce, d.bmod, "k_batch_reduce"));
-    HIPCHK(hipMalloc(&d.d_small_part, sizeof(Key) * kSmallMaxBlocks));
-    HIPCHK(hipMalloc(&d.d_ticket, sizeof(uint32_t)));
-    HIPCHK(hipMalloc(&d.d_scan_ticket, 2 * sizeof(uint32_t)));
-    // on the library's own stream: a null-stream call would give every
-    // process a second hardware queue (8 miner processes share one GPU)
-    HIPCHK(hipMemsetAsync(d.d_ticket, 0, sizeof(uint32_t), d.stream));
-    HIPCHK(hipMemsetAsync(d.d_scan_ticket, 0, 2 * sizeof(uint32_t), d.stream));
-    // k_scan's grid: every workgroup slot of the device once (the work queue
-    // hands the tiles out; p1hip_kernels.hip k_scan)
-    {
-      hipDeviceProp_t prop;
-      HIPCHK(hipGetDeviceProperties(&prop, d.ordinal));
-      int per_cu = 0;
-      HIPCHK(hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, d.f_scan, kBlock, 0));
-      if (per_cu < 1 || prop.multiProcessorCount < 1)
-        return fail(P1HIP_ERR_HIP, "k_scan occupancy: " + std::to_string(per_cu) + " blocks per CU");
-      d.scan_grid = (uint32_t)per_cu * (uint32_t)prop.multiProcessorCount;
-    }
-    HIPCHK(hipStreamSynchronize(d.stream));
-    HIPCHK(hipMalloc(&d.d_res, sizeof(Key)));
-    HIPCHK(hipMalloc(&d.d_gather, sizeof(Key) * nd));
-    HIPCHK(hipHostMalloc(&d.h_res, sizeof(Key) * nd, hipHostMallocDefault));
-  }
-  // P1HIP_NO_RCCL=1 (tests only): combine the per-device results through the
-  // host instead of RCCL, so the multi-device code path (threads, sharding,
-  // combine) can be exercised with the same GPU listed twice on a 1-GPU box.
-  const char* norccl = test_knob("P1HIP_NO_RCCL");
-  R.use_rccl = !(norccl && norccl[0] == '1');
-  const char* force = test_knob("P1HIP_FORCE_RCCL");
-  R.rccl_one = force && force[0] == '1' && R.use_rccl;
-  const char* mft = test_knob("P1HIP_MIN_FAST_THREADS");
-  R.min_fast_threads = mft ? strtoull(mft, nullptr, 10) : kMinFastThreads;
-  const char* nsp = test_knob("P1HIP_NO_SPLIT");
-  R.split = !(nsp && nsp[0] == '1');
-  const char* ntb = test_knob("P1HIP_NO_TABLE");
-  R.tabulate = !(ntb && ntb[0] == '1');
-  const char* fdev = test_knob("P1HIP_TEST_FAIL_DEVICE");
-  R.fail_device = fdev ? atoi(fdev) : -1;
-  if ((nd > 1 || R.rccl_one) && R.use_rccl) {
-    std::vector<ncclComm_t> comms(nd);
-    NCCLCHK(ncclCommInitAll(comms.data(), nd, ords.data()));
-    for (int i = 0; i < nd; ++i) R.devs[i].comm = comms[i];
-  }
-  return P1HIP_OK;
-}
-
-// hipModuleLaunchKernel with the arguments as a pointer array
-template <typename... Args>
-hipError_t launch(hipFunction_t f, uint32_t blocks, uint32_t threads, hipStream_t st, Args... args) {
-  void* params[] = {(void*)&args...};
-  return hipModuleLaunchKernel(f, blocks, 1, 1, threads, 1, 1, 0, st, params, nullptr);
-}
-
 int ensure_init(Runtime& R) {
   if (!R.devs.empty()) return P1HIP_OK;
   int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
-    return fail(P1HIP_ERR_NO_DEVICE, "no HIP device visible");
+  if (int rc = device_count(&count)) return rc;
   std::vector<int> ords;
   for (int i = 0; i < count; ++i) ords.push_back(i);
   return init_locked(R, ords);
 }
 
+// ----------------------------------------------------------------------------
+// p1hip_scan
+// ----------------------------------------------------------------------------
 // Small share [lo, hi] (at most kSmallMaxNonces nonces): one k_scan_small
 // launch; the Key lands in d.d_res and, when `to_host`, in d.h_res[0].
 int run_small(Dev& d, const uint8_t* msg, size_t len, uint64_t lo, uint64_t hi, bool to_host, bool profiling) {
   HIPCHK(hipSetDevice(d.ordinal));
-  d.fast_launches = d.fast_nonces = d.fast_ops = d.gen_launches = d.gen_nonces = 0;
-  d.scan_launches = d.scan_nonces = d.scan_ops = 0;
-  d.scan_ms = 0.0;
+  d.ctr = {};
   Plan plan;
   std::string err = make_plan(msg, len, lo, hi, plan, false);
   if (!err.empty()) return fail(P1HIP_ERR_ARGS, "planner: " + err);
-  if (plan.launches.size() > kSmallMaxSegs || plan.total_blocks > kSmallMaxBlocks)
-    return fail(P1HIP_ERR_ARGS, "internal: small plan exceeds its argument block");
   SmallArgs a;
-  memset(&a, 0, sizeof a);
-  uint32_t block0 = 0;
-  for (size_t i = 0; i < plan.launches.size(); ++i) {
-    const Launch& L = plan.launches[i];
-    a.ga[i] = L.ga;
-    a.block0[i] = block0;
-    block0 += L.blocks;
-    d.gen_launches++;
-    d.gen_nonces += L.nonces;
-    d.scan_ops += L.nonces * kAlgOpsPerCompression * (uint64_t)L.btail;
-  }
-  a.nseg = (uint32_t)plan.launches.size();
-  a.nblocks = block0;
-  a.part = d.d_small_part;
-  a.ticket = d.d_ticket;
-  a.out_dev = d.d_res;
-  a.out_host = to_host ? d.h_res : nullptr;
-  if (profiling) {
-    while (d.evs.size() < 2) {
-      hipEvent_t e;
-      HIPCHK(hipEventCreate(&e));
-      d.evs.push_back(e);
-    }
-    HIPCHK(hipEventRecord(d.evs[0], d.stream));
-  }
+  err = fill_small(plan, a, d.ctr);
+  if (!err.empty()) return fail(P1HIP_ERR_ARGS, err);
+  a.part = d.d_small_part.p;
+  a.ticket = d.d_ticket.p;
+  a.out_dev = d.d_res.p;
+  a.out_host = to_host ? d.h_res.p : nullptr;
+  int rc;
+  size_t nev = 0;
+  if (profiling && (rc = ev_record(d, nev))) return rc;
   HIPCHK(launch(d.f_small, a.nblocks, kBlock, d.stream, a));
-  if (profiling) {
-    float ms = 0.f;
-    HIPCHK(hipEventRecord(d.evs[1], d.stream));
-    HIPCHK(hipEventSynchronize(d.evs[1]));
-    HIPCHK(hipEventElapsedTime(&ms, d.evs[0], d.evs[1]));
-    d.scan_ms = ms;
-  }
-  d.scan_launches = 1;
-  d.scan_nonces = plan.total_nonces;
-  return P1HIP_OK;
+  if (profiling && (rc = ev_record(d, nev))) return rc;
+  return ev_sum(d, nev);
 }
 
 // Device copy of a MODE 5 launch's K+W table (cached, least recently used
 // evicted: the same layout in later scans reuses it; scans are synchronous,
 // so an evicted table is idle).
-constexpr size_t kMaxKwTabs = 8;
-// ... and at most this many bytes of them (a 7-digit table is 2.56 GB; one
-// scan needs at most one table per MODE 5 decade, < 2.9 GB in all)
-constexpr size_t kMaxKwTabBytes = (size_t)8 << 30;
 // kNoTable: the table cannot be had (larger than the cap, or the device is
 // out of memory); the caller re-plans the share without MODE 5.
 constexpr int kNoTable = 1;
@@ -480,9 +529,7 @@ int kwtable_for(Dev& d, const Launch& L, uint64_t* dptr) {
     }
   }
   const size_t need = (size_t)pow10u(L.tabk) * 64u * sizeof(uint32_t);
-  // P1HIP_KWTAB_MAX_BYTES (tests only): a lower cap, to exercise the re-plan
-  const char* capv = test_knob("P1HIP_KWTAB_MAX_BYTES");
-  const size_t cap = capv ? (size_t)strtoull(capv, nullptr, 10) : kMaxKwTabBytes;
+  const size_t cap = (size_t)knob(kKwtabMaxBytesKnob);
   if (need > cap) return kNoTable;
   for (;;) {
     size_t held = 0;
@@ -526,15 +573,11 @@ int kwtable_for(Dev& d, const Launch& L, uint64_t* dptr) {
   return P1HIP_OK;
 }
 
-// P1HIP_SCAN_GRID (tests / A/B only, read per scan): k_scan's grid instead of
-// the device's workgroup slots; at or above a launch's tile count every
-// workgroup runs one tile and the queue hands out none (the round-5
-// dispatch, on the same code object).
+// k_scan's grid for a launch of `tiles` tiles: the device's workgroup slots,
+// or P1HIP_SCAN_GRID
 uint32_t scan_grid_for(const Dev& d, uint32_t tiles) {
-  const char* v = test_knob("P1HIP_SCAN_GRID");
-  const uint64_t g = v ? strtoull(v, nullptr, 10) : 0;
-  const uint32_t slots = g > 0 ? (uint32_t)std::min<uint64_t>(g, kMaxLaunchBlocks) : d.scan_grid;
-  return std::min(tiles, slots);
+  const uint64_t g = knob(kScanGridKnob);
+  return std::min(tiles, g > 0 ? (uint32_t)g : d.scan_grid);
 }
 
 // Run one device's share [lo, hi] (lo <= hi) and leave its Key in d.d_res.
@@ -542,9 +585,7 @@ int run_range(Dev& d, const uint8_t* msg, size_t len, uint64_t lo, uint64_t hi, 
               uint64_t min_fast_threads, bool split, bool tabulate) {
   HIPCHK(hipSetDevice(d.ordinal));
   d.range_id++;  // tables referenced from here on are pinned until the next call
-  d.fast_launches = d.fast_nonces = d.fast_ops = d.gen_launches = d.gen_nonces = 0;
-  d.scan_launches = d.scan_nonces = d.scan_ops = 0;
-  d.scan_ms = 0.0;
+  d.ctr = {};
   Plan plan;
   // plan -> every MODE 5 table -> launches: a table that cannot be had makes
   // the share re-plan without MODE 5 here, before any k_scan of it (or any
@@ -569,124 +610,34 @@ int run_range(Dev& d, const uint8_t* msg, size_t len, uint64_t lo, uint64_t hi, 
     d.replans++;
     plan = Plan();
   }
-  // Longest-running workgroups first: fast pieces by lo-loop length (10^k),
-  // then generic pieces, so short work fills the grid's drain.
-  std::vector<size_t> order(plan.launches.size());
-  for (size_t i = 0; i < order.size(); ++i) order[i] = i;
-  auto weight = [&](size_t i) -> uint64_t {
-    const Launch& L = plan.launches[i];
-    return L.fast ? (uint64_t)(L.fa.kpow / L.fa.nsub) * (uint64_t)L.btail : (uint64_t)L.btail - 1;
-  };
-  std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return weight(a) > weight(b); });
-  // Pack into launches of <= kMaxSegs segments / kMaxLaunchBlocks workgroups.
-  // When a scan needs several launches (e.g. configs[3]'s 2^38 nonces on one
-  // GPU), balance them: each batch closes once it reaches total/launches
-  // workgroups, so the launches are near-equal rather than one full and one
-  // small one (equal drains, and a per-launch average that means something).
-  struct Batch { size_t first, count; uint32_t blocks; };
-  std::vector<Batch> batches;
-  uint64_t all_blocks = 0;
-  for (const Launch& L : plan.launches) all_blocks += L.blocks;
-  const uint64_t max_blocks = launch_block_limit();
-  const uint64_t nlaunch = (all_blocks + max_blocks - 1) / max_blocks;
-  const uint64_t target = nlaunch > 1 ? (all_blocks + nlaunch - 1) / nlaunch : max_blocks;
-  uint32_t total_blocks = 0;
-  for (size_t r = 0; r < order.size(); ++r) {
-    const Launch& L = plan.launches[order[r]];
-    const uint64_t cur = batches.empty() ? 0 : batches.back().blocks;
-    if (batches.empty() || batches.back().count == kMaxSegs || cur + (uint64_t)L.blocks > max_blocks ||
-        (cur > 0 && cur + L.blocks / 2 > target && batches.size() < nlaunch))  // fits the next batch better
-      batches.push_back({r, 0, 0});
-    batches.back().count++;
-    batches.back().blocks += L.blocks;
-    total_blocks += L.blocks;
-  }
-  if (total_blocks > d.part_cap) {
-    if (d.d_part) HIPCHK(hipFree(d.d_part));
-    d.d_part = nullptr;
-    size_t cap = 1;
-    while (cap < total_blocks) cap <<= 1;
-    HIPCHK(hipMalloc(&d.d_part, cap * sizeof(Key)));
-    d.part_cap = cap;
-  }
-  if (batches.size() > d.seg_cap) {
-    if (d.d_seg) HIPCHK(hipFree(d.d_seg));
-    if (d.h_seg) HIPCHK(hipHostFree(d.h_seg));
-    d.d_seg = nullptr;
-    d.h_seg = nullptr;
-    size_t cap = 4;
-    while (cap < batches.size()) cap <<= 1;
-    HIPCHK(hipMalloc(&d.d_seg, cap * kMaxSegs * sizeof(Segment)));
-    HIPCHK(hipHostMalloc(&d.h_seg, cap * kMaxSegs * sizeof(Segment), hipHostMallocDefault));
-    d.seg_cap = cap;
-  }
+  const ScanPack P = pack_scan(plan, knob(kMaxLaunchBlocksKnob));
+  HIPCHK(d.d_part.reserve(P.total_blocks, 1));
+  HIPCHK(d.d_seg.reserve(P.batches.size() * kMaxSegs, 4 * kMaxSegs));
+  HIPCHK(d.h_seg.reserve(P.batches.size() * kMaxSegs, 4 * kMaxSegs));
+  int rc;
   size_t nev = 0;
   uint32_t part_off = 0;
-  for (size_t bi = 0; bi < batches.size(); ++bi) {
-    const Batch& B = batches[bi];
-    Segment* hs = d.h_seg + bi * kMaxSegs;
-    uint64_t ops = 0, nonces = 0;
-    uint32_t block0 = 0;
-    for (size_t j = 0; j < B.count; ++j) {
-      const Launch& L = plan.launches[order[B.first + j]];
-      Segment& S = hs[j];
-      memset(&S, 0, sizeof S);
-      S.block0 = block0;
-      block0 += L.blocks;
-      if (L.fast) {
-        if (!has_variant(L.fv, L.mode, L.trail)) return fail(P1HIP_ERR_ARGS, "no fast kernel variant");
-        S.kind = variant_id(L.fv, L.mode, L.trail);
-        S.fa = L.fa;
-        if (L.mode == 5 || L.mode == 7) S.fa.kwtab = tabptr[order[B.first + j]];
-        d.fast_launches++;
-        d.fast_nonces += L.nonces;
-        d.fast_ops += L.nonces * kAlgOpsPerCompression * (uint64_t)L.btail;
-      } else {
-        S.kind = kGenericKind;
-        S.ga = L.ga;
-        d.gen_launches++;
-        d.gen_nonces += L.nonces;
-      }
-      nonces += L.nonces;
-      ops += L.nonces * kAlgOpsPerCompression * (uint64_t)L.btail;
-    }
-    Segment* ds = d.d_seg + bi * kMaxSegs;
+  for (size_t bi = 0; bi < P.batches.size(); ++bi) {
+    const ScanBatch& B = P.batches[bi];
+    Segment* hs = d.h_seg.p + bi * kMaxSegs;
+    Segment* ds = d.d_seg.p + bi * kMaxSegs;
+    const std::string err = fill_segments(plan, P, B, tabptr.data(), hs, d.ctr);
+    if (!err.empty()) return fail(P1HIP_ERR_ARGS, err);
     HIPCHK(hipMemcpyAsync(ds, hs, B.count * sizeof(Segment), hipMemcpyHostToDevice, d.stream));
-    if (profiling) {
-      while (d.evs.size() < nev + 2) {
-        hipEvent_t e;
-        HIPCHK(hipEventCreate(&e));
-        d.evs.push_back(e);
-      }
-      HIPCHK(hipEventRecord(d.evs[nev], d.stream));
-    }
+    if (profiling && (rc = ev_record(d, nev))) return rc;
 #ifdef P1_STATIC_GRID
     HIPCHK(launch(d.f_scan, B.blocks, kBlock, d.stream, (const Segment*)ds, (uint32_t)B.count,
-                  (Key*)(d.d_part + part_off)));
+                  (Key*)(d.d_part.p + part_off)));
 #else
     // B.blocks tiles through a work queue on min(tiles, slots) workgroups
     HIPCHK(launch(d.f_scan, scan_grid_for(d, B.blocks), kBlock, d.stream, (const Segment*)ds,
-                  (uint32_t)B.count, (Key*)(d.d_part + part_off), (uint32_t)B.blocks, d.d_scan_ticket));
+                  (uint32_t)B.count, (Key*)(d.d_part.p + part_off), (uint32_t)B.blocks, d.d_scan_ticket.p));
 #endif
-    if (profiling) {
-      HIPCHK(hipEventRecord(d.evs[nev + 1], d.stream));
-      nev += 2;
-    }
+    if (profiling && (rc = ev_record(d, nev))) return rc;
     part_off += B.blocks;
-    d.scan_launches++;
-    d.scan_nonces += nonces;
-    d.scan_ops += ops;
   }
-  HIPCHK(launch(d.f_reduce, 1, kReduceThreads, d.stream, (const Key*)d.d_part, total_blocks, d.d_res));
-  if (profiling && nev) {
-    HIPCHK(hipEventSynchronize(d.evs[nev - 1]));
-    for (size_t i = 0; i < nev; i += 2) {
-      float ms = 0.f;
-      HIPCHK(hipEventElapsedTime(&ms, d.evs[i], d.evs[i + 1]));
-      d.scan_ms += ms;
-    }
-  }
-  return P1HIP_OK;
+  HIPCHK(launch(d.f_reduce, 1, kReduceThreads, d.stream, (const Key*)d.d_part.p, P.total_blocks, d.d_res.p));
+  return ev_sum(d, nev);
 }
 
 // A device's share, in pieces of at most kMaxScanSpan nonces: the plan of a
@@ -695,98 +646,29 @@ int run_range(Dev& d, const uint8_t* msg, size_t len, uint64_t lo, uint64_t hi, 
 // pieces.  Each piece is a full run_range; the keys are combined on the host
 // and the result written back to d.d_res.  Shares up to 2^40 nonces (about
 // 30 s of one GPU) are a single piece, with no extra copy.
-constexpr uint64_t kMaxScanSpan = 1ull << 40;
 int run_share(Dev& d, const uint8_t* msg, size_t len, uint64_t lo, uint64_t hi, const Runtime& R) {
-  // P1HIP_MAX_SCAN_SPAN (tests only, read per scan): smaller pieces
-  const char* sv = test_knob("P1HIP_MAX_SCAN_SPAN");
-  const uint64_t span = sv && strtoull(sv, nullptr, 10) > 0 ? strtoull(sv, nullptr, 10) : kMaxScanSpan;
+  const uint64_t span = knob(kMaxScanSpanKnob);
   if (hi - lo < span)
     return run_range(d, msg, len, lo, hi, R.profiling, R.min_fast_threads, R.split, R.tabulate);
   Key best = {~0ull, ~0ull};
-  uint64_t fl = 0, fn = 0, fo = 0, gl = 0, gn = 0, sl = 0, sn = 0, so = 0;
-  double sms = 0.0;
+  ScanCounters sum;
   for (uint64_t a = lo;;) {
     const uint64_t b = hi - a < span ? hi : a + (span - 1);
     int r = run_range(d, msg, len, a, b, R.profiling, R.min_fast_threads, R.split, R.tabulate);
     if (r != P1HIP_OK) return r;
     Key k;
-    HIPCHK(hipMemcpyAsync(&k, d.d_res, sizeof(Key), hipMemcpyDeviceToHost, d.stream));
+    HIPCHK(hipMemcpyAsync(&k, d.d_res.p, sizeof(Key), hipMemcpyDeviceToHost, d.stream));
     HIPCHK(hipStreamSynchronize(d.stream));
     if (key_lt(k, best)) best = k;
-    fl += d.fast_launches; fn += d.fast_nonces; fo += d.fast_ops; gl += d.gen_launches; gn += d.gen_nonces;
-    sl += d.scan_launches; sn += d.scan_nonces; so += d.scan_ops; sms += d.scan_ms;
+    sum += d.ctr;
     if (b == hi) break;
     a = b + 1;
   }
-  d.fast_launches = fl; d.fast_nonces = fn; d.fast_ops = fo; d.gen_launches = gl; d.gen_nonces = gn;
-  d.scan_launches = sl; d.scan_nonces = sn; d.scan_ops = so; d.scan_ms = sms;
-  HIPCHK(hipMemcpyAsync(d.d_res, &best, sizeof(Key), hipMemcpyHostToDevice, d.stream));
+  d.ctr = sum;
+  HIPCHK(hipMemcpyAsync(d.d_res.p, &best, sizeof(Key), hipMemcpyHostToDevice, d.stream));
   HIPCHK(hipStreamSynchronize(d.stream));  // `best` lives on this stack frame
   return P1HIP_OK;
 }
-
-Key finish_key(Key k) {
-  if (k.h == ~0ull) k.n = 0;  // identity (MaxUint64, 0) of miner.go:56
-  return k;
-}
-
-int scan_locked(const uint8_t* msg, size_t msg_len, uint64_t lower, uint64_t upper, uint64_t* out_hash,
-                uint64_t* out_nonce);
-int scan_batch_locked(const p1hip_request_t* reqs, size_t n, p1hip_result_t* out);
-int reduce_pairs_locked(const uint64_t* hashes, const uint64_t* nonces, size_t n, uint64_t* out_hash,
-                        uint64_t* out_nonce);
-
-}  // namespace
-
-// ----------------------------------------------------------------------------
-// C ABI
-// ----------------------------------------------------------------------------
-extern "C" {
-
-int p1hip_init(int want_devices, int* got_devices) {
-  if (got_devices) *got_devices = 0;
-  return guarded([&]() {
-    Runtime& R = rt();
-    std::lock_guard<std::mutex> g(R.mu);
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
-      return fail(P1HIP_ERR_NO_DEVICE, "no HIP device visible");
-    int n = want_devices <= 0 ? count : want_devices;
-    if (n > count) return fail(P1HIP_ERR_NO_DEVICE, "asked for more devices than visible");
-    std::vector<int> ords;
-    for (int i = 0; i < n; ++i) ords.push_back(i);
-    int rc = init_locked(R, ords);
-    if (got_devices) *got_devices = rc == 0 ? (int)R.devs.size() : 0;
-    return rc;
-  });
-}
-
-int p1hip_init_devices(const int* ordinals, int n) {
-  if (!ordinals || n <= 0) return fail(P1HIP_ERR_ARGS, "empty device list");
-  return guarded([&]() {
-    Runtime& R = rt();
-    std::lock_guard<std::mutex> g(R.mu);
-    return init_locked(R, std::vector<int>(ordinals, ordinals + n));
-  });
-}
-
-int p1hip_device_count(void) {
-  Runtime& R = rt();
-  std::lock_guard<std::mutex> g(R.mu);
-  return (int)R.devs.size();
-}
-
-int p1hip_scan(const uint8_t* msg, size_t msg_len, uint64_t lower, uint64_t upper, uint64_t* out_hash,
-               uint64_t* out_nonce) {
-  if (!out_hash || !out_nonce) return fail(P1HIP_ERR_ARGS, "null output pointer");
-  if (!msg && msg_len > 0) return fail(P1HIP_ERR_ARGS, "msg == NULL with msg_len > 0");
-  if (msg_len > P1HIP_MAX_MSG_LEN) return fail(P1HIP_ERR_ARGS, "msg_len exceeds P1HIP_MAX_MSG_LEN");
-  return guarded([&]() { return scan_locked(msg, msg_len, lower, upper, out_hash, out_nonce); });
-}
-
-}  // extern "C"
-
-namespace {
 
 // One scan with R.mu held by the caller (p1hip_scan; p1hip_scan_batch for the
 // requests it runs individually).
@@ -832,30 +714,52 @@ int scan_held(Runtime& R, const uint8_t* msg, size_t msg_len, uint64_t lower, ui
         for (auto& t : th) t.join();
       }
     };
-    auto first_error = [&]() -> int {
+    // One phase on every device: body(i, d) is device i's work and returns
+    // its rc.  A host exception inside a device thread would end the process
+    // (std::terminate): it becomes this device's rc instead, with the message
+    // if building it does not throw as well.  The phase's wall time is added
+    // to the device's `ms`.
+    auto run_phase = [&](double p1hip_device_stats_t::*ms, auto&& body) {
+      run_threads([&](size_t i) {
+        Dev& d = R.devs[i];
+        const auto p0 = std::chrono::steady_clock::now();
+        int r;
+        try {
+          r = body(i, d);
+        } catch (const std::exception& ex) {
+          try {
+            r = fail(P1HIP_ERR_HIP, std::string("host: ") + ex.what());
+          } catch (...) {
+            r = P1HIP_ERR_HIP;
+          }
+        } catch (...) {
+          r = P1HIP_ERR_HIP;
+        }
+        d.acc.*ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - p0).count();
+        rcs[i] = r;
+        if (r) {
+          try {
+            errs[i] = g_err;
+          } catch (...) {  // the copy allocates; rcs[i] already says what matters
+          }
+        }
+      });
       for (size_t i = 0; i < nd; ++i)
         if (rcs[i]) return fail(rcs[i], "device " + std::to_string(R.devs[i].ordinal) + ": " + errs[i]);
-      return P1HIP_OK;
+      return (int)P1HIP_OK;
     };
     const bool coll = (nd > 1 || R.rccl_one) && R.use_rccl;
-    const uint64_t small_max = small_limit();
-    run_threads([&](size_t i) {
-      Dev& d = R.devs[i];
-      int r = P1HIP_OK;
-      const auto p0 = std::chrono::steady_clock::now();
+    const uint64_t small_max = knob(kSmallMaxNoncesKnob);
+    rc = run_phase(&p1hip_device_stats_t::phase1_ms, [&](size_t i, Dev& d) -> int {
       // per-scan accounting starts empty on every device (an inactive shard
       // must not re-report its previous scan)
-      d.fast_launches = d.fast_nonces = d.fast_ops = d.gen_launches = d.gen_nonces = 0;
-      d.scan_launches = d.scan_nonces = d.scan_ops = 0;
-      d.scan_ms = 0.0;
+      d.ctr = {};
       d.replans = 0;
       d.small_used = false;
       d.acc.shard_first = slo[i];
       d.acc.shard_last = shi[i];
       d.acc.active = active[i];
-      // a host exception inside a device thread would end the process
-      // (std::terminate): it becomes this device's error instead
-      try {
+      int r = P1HIP_OK;
       if ((int)i == R.fail_device) {
         r = fail(P1HIP_ERR_HIP, "injected failure (P1HIP_TEST_FAIL_DEVICE)");
       } else if (active[i] && shi[i] - slo[i] < small_max) {
@@ -866,86 +770,46 @@ int scan_held(Runtime& R, const uint8_t* msg, size_t msg_len, uint64_t lower, ui
       } else {
         // empty shard: contribute the identity key (all ones)
         if (hipSetDevice(d.ordinal) != hipSuccess) r = fail(P1HIP_ERR_HIP, "hipSetDevice");
-        if (!r && hipMemsetAsync(d.d_res, 0xFF, sizeof(Key), d.stream) != hipSuccess)
+        if (!r && hipMemsetAsync(d.d_res.p, 0xFF, sizeof(Key), d.stream) != hipSuccess)
           r = fail(P1HIP_ERR_HIP, "hipMemsetAsync(identity)");
       }
       if (!r && !coll && nd > 1) {  // host combine (P1HIP_NO_RCCL, tests)
-        if (hipMemcpyAsync(R.devs[0].h_res + i, d.d_res, sizeof(Key), hipMemcpyDeviceToHost, d.stream) != hipSuccess)
+        if (hipMemcpyAsync(R.devs[0].h_res.p + i, d.d_res.p, sizeof(Key), hipMemcpyDeviceToHost, d.stream) !=
+            hipSuccess)
           r = fail(P1HIP_ERR_HIP, "hipMemcpyAsync(result)");
       } else if (!r && !coll && !(active[i] && d.small_used)) {  // the small kernel wrote h_res itself
-        if (hipMemcpyAsync(d.h_res, d.d_res, sizeof(Key), hipMemcpyDeviceToHost, d.stream) != hipSuccess)
+        if (hipMemcpyAsync(d.h_res.p, d.d_res.p, sizeof(Key), hipMemcpyDeviceToHost, d.stream) != hipSuccess)
           r = fail(P1HIP_ERR_HIP, "hipMemcpyAsync(result)");
       }
       if (!r && hipStreamSynchronize(d.stream) != hipSuccess) r = fail(P1HIP_ERR_HIP, "hipStreamSynchronize");
-      } catch (const std::exception& ex) {
-        try {
-          r = fail(P1HIP_ERR_HIP, std::string("host: ") + ex.what());
-        } catch (...) {
-          r = P1HIP_ERR_HIP;
-        }
-      } catch (...) {
-        r = P1HIP_ERR_HIP;
-      }
-      d.acc.phase1_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - p0).count();
-      rcs[i] = r;
-      if (r) {
-        try {
-          errs[i] = g_err;
-        } catch (...) {  // the copy allocates; rcs[i] already says what matters
-        }
-      }
+      return r;
     });
-    if ((rc = first_error()) != P1HIP_OK) return rc;
+    if (rc != P1HIP_OK) return rc;
     if (coll) {
       // Phase 2: all-gather the 16-byte partials (2 x u64 per device) over
       // RCCL; device 0 copies the gathered table to the host.  One group call
       // per device thread is not needed: each thread enqueues on its own
       // communicator and the collective completes when all have joined.
-      run_threads([&](size_t i) {
-        Dev& d = R.devs[i];
-        int r = P1HIP_OK;
-        const auto g0 = std::chrono::steady_clock::now();
-        // as in phase 1: a host exception (the error strings below allocate)
-        // becomes this device's rc, never std::terminate
-        try {
-        if (hipSetDevice(d.ordinal) != hipSuccess) r = fail(P1HIP_ERR_HIP, "hipSetDevice");
-        if (!r) {
-          ncclResult_t nr = ncclAllGather(d.d_res, d.d_gather, 2, ncclUint64, d.comm, d.stream);
-          if (nr != ncclSuccess) r = fail(P1HIP_ERR_RCCL, std::string("ncclAllGather: ") + ncclGetErrorString(nr));
-        }
-        if (!r && i == 0 &&
-            hipMemcpyAsync(d.h_res, d.d_gather, sizeof(Key) * nd, hipMemcpyDeviceToHost, d.stream) != hipSuccess)
-          r = fail(P1HIP_ERR_HIP, "hipMemcpyAsync(gathered)");
-        if (!r && hipStreamSynchronize(d.stream) != hipSuccess) r = fail(P1HIP_ERR_HIP, "hipStreamSynchronize");
-        d.acc.gather_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - g0).count();
-        rcs[i] = r;
-        if (r) errs[i] = g_err;
-        } catch (...) {
-          rcs[i] = P1HIP_ERR_HIP;  // errs[i] stays empty: building it may be what threw
-        }
+      rc = run_phase(&p1hip_device_stats_t::gather_ms, [&](size_t i, Dev& d) -> int {
+        if (hipSetDevice(d.ordinal) != hipSuccess) return fail(P1HIP_ERR_HIP, "hipSetDevice");
+        ncclResult_t nr = ncclAllGather(d.d_res.p, d.d_gather.p, 2, ncclUint64, d.comm, d.stream);
+        if (nr != ncclSuccess) return fail(P1HIP_ERR_RCCL, std::string("ncclAllGather: ") + ncclGetErrorString(nr));
+        if (i == 0 &&
+            hipMemcpyAsync(d.h_res.p, d.d_gather.p, sizeof(Key) * nd, hipMemcpyDeviceToHost, d.stream) != hipSuccess)
+          return fail(P1HIP_ERR_HIP, "hipMemcpyAsync(gathered)");
+        if (hipStreamSynchronize(d.stream) != hipSuccess) return fail(P1HIP_ERR_HIP, "hipStreamSynchronize");
+        return P1HIP_OK;
       });
-      if ((rc = first_error()) != P1HIP_OK) return rc;
+      if (rc != P1HIP_OK) return rc;
     }
     Key b = {~0ull, ~0ull};
-    for (size_t i = 0; i < nd; ++i) b = key_lt(R.devs[0].h_res[i], b) ? R.devs[0].h_res[i] : b;
+    for (size_t i = 0; i < nd; ++i) b = key_lt(R.devs[0].h_res.p[i], b) ? R.devs[0].h_res.p[i] : b;
     res = finish_key(b);
     for (Dev& d : R.devs) {
-      R.stats.fast_launches += d.fast_launches;
-      R.stats.fast_nonces += d.fast_nonces;
-      R.stats.fast_alg_ops += d.fast_ops;
-      R.stats.generic_launches += d.gen_launches;
-      R.stats.generic_nonces += d.gen_nonces;
-      R.stats.scan_launches += d.scan_launches;
-      R.stats.scan_nonces += d.scan_nonces;
-      R.stats.scan_alg_ops += d.scan_ops;
-      R.stats.scan_kernel_ms += d.scan_ms;
-      if (d.small_used && d.scan_launches) R.stats.small_scans++;
+      add_counters(R.stats, d.ctr);
+      add_counters(d.acc, d.ctr);
+      if (d.small_used && d.ctr.scan_launches) R.stats.small_scans++;
       R.stats.table_replans += d.replans;
-      d.acc.scans++;
-      d.acc.scan_launches += d.scan_launches;
-      d.acc.scan_nonces += d.scan_nonces;
-      d.acc.scan_alg_ops += d.scan_ops;
-      d.acc.scan_kernel_ms += d.scan_ms;
     }
   }
   R.stats.scans++;
@@ -986,47 +850,13 @@ std::vector<BatchReq> batch_reqs(const p1hip_request_t* reqs, size_t n) {
 // `tiles` tiles.  Called only while the stream is idle (every round of
 // scan_batch_locked ends with a synchronisation).
 int batch_reserve(Dev& d, size_t nseg, size_t nreq, size_t tiles) {
-  auto grown = [](size_t need, size_t floor) {
-    size_t cap = floor;
-    while (cap < need) cap <<= 1;
-    return cap;
-  };
-  if (nseg > d.bseg_cap) {
-    if (d.d_bseg) HIPCHK(hipFree(d.d_bseg));
-    d.d_bseg = nullptr;
-    if (d.h_bseg) HIPCHK(hipHostFree(d.h_bseg));
-    d.h_bseg = nullptr;
-    d.bseg_cap = 0;
-    const size_t cap = grown(nseg, 64);
-    HIPCHK(hipMalloc(&d.d_bseg, cap * sizeof(BatchSeg)));
-    HIPCHK(hipHostMalloc(&d.h_bseg, cap * sizeof(BatchSeg), hipHostMallocDefault));
-    d.bseg_cap = cap;
-  }
-  if (nreq > d.breq_cap) {
-    if (d.d_btile0) HIPCHK(hipFree(d.d_btile0));
-    d.d_btile0 = nullptr;
-    if (d.h_btile0) HIPCHK(hipHostFree(d.h_btile0));
-    d.h_btile0 = nullptr;
-    if (d.d_bout) HIPCHK(hipFree(d.d_bout));
-    d.d_bout = nullptr;
-    if (d.h_bout) HIPCHK(hipHostFree(d.h_bout));
-    d.h_bout = nullptr;
-    d.breq_cap = 0;
-    const size_t cap = grown(nreq, 64);
-    HIPCHK(hipMalloc(&d.d_btile0, (cap + 1) * sizeof(uint32_t)));
-    HIPCHK(hipHostMalloc(&d.h_btile0, (cap + 1) * sizeof(uint32_t), hipHostMallocDefault));
-    HIPCHK(hipMalloc(&d.d_bout, cap * sizeof(Key)));
-    HIPCHK(hipHostMalloc(&d.h_bout, cap * sizeof(Key), hipHostMallocDefault));
-    d.breq_cap = cap;
-  }
-  if (tiles > d.bpart_cap) {
-    if (d.d_bpart) HIPCHK(hipFree(d.d_bpart));
-    d.d_bpart = nullptr;
-    d.bpart_cap = 0;
-    const size_t cap = grown(tiles, 1024);
-    HIPCHK(hipMalloc(&d.d_bpart, cap * sizeof(Key)));
-    d.bpart_cap = cap;
-  }
+  HIPCHK(d.d_bseg.reserve(nseg, 64));
+  HIPCHK(d.h_bseg.reserve(nseg, 64));
+  HIPCHK(d.d_btile0.reserve(nreq, 64, 1));
+  HIPCHK(d.h_btile0.reserve(nreq, 64, 1));
+  HIPCHK(d.d_bout.reserve(nreq, 64));
+  HIPCHK(d.h_bout.reserve(nreq, 64));
+  HIPCHK(d.d_bpart.reserve(tiles, 1024));
   return P1HIP_OK;
 }
 
@@ -1037,7 +867,8 @@ int scan_batch_locked(const p1hip_request_t* reqs, size_t n, p1hip_result_t* out
   int rc = ensure_init(R);
   if (rc) return rc;
   const std::vector<BatchReq> q = batch_reqs(reqs, n);
-  const BatchLayout Y = batch_layout(q.data(), n, (int)R.devs.size(), batch_nonce_limit(), batch_tile_limit());
+  const BatchLayout Y =
+      batch_layout(q.data(), n, (int)R.devs.size(), knob(kBatchMaxNoncesKnob), knob(kBatchMaxTilesKnob));
   // results are gathered here and copied to `out` only when the whole call
   // has succeeded
   std::vector<p1hip_result_t> res(n, p1hip_result_t{~0ull, 0});
@@ -1061,14 +892,16 @@ int scan_batch_locked(const p1hip_request_t* reqs, size_t n, p1hip_result_t* out
         const size_t nseg = T.segs.size(), nreq = L->reqs.size();
         HIPCHK(hipSetDevice(d.ordinal));
         if ((rc = batch_reserve(d, nseg, nreq, L->tiles)) != P1HIP_OK) return rc;
-        memcpy(d.h_bseg, T.segs.data(), nseg * sizeof(BatchSeg));
-        memcpy(d.h_btile0, T.req_tile0.data(), (nreq + 1) * sizeof(uint32_t));
-        HIPCHK(hipMemcpyAsync(d.d_bseg, d.h_bseg, nseg * sizeof(BatchSeg), hipMemcpyHostToDevice, d.stream));
-        HIPCHK(hipMemcpyAsync(d.d_btile0, d.h_btile0, (nreq + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, d.stream));
-        HIPCHK(launch(d.f_bscan, L->tiles, kBlock, d.stream, (const BatchSeg*)d.d_bseg, (uint32_t)nseg, d.d_bpart));
-        HIPCHK(launch(d.f_breduce, (uint32_t)nreq, kBlock, d.stream, (const Key*)d.d_bpart,
-                      (const uint32_t*)d.d_btile0, d.d_bout));
-        HIPCHK(hipMemcpyAsync(d.h_bout, d.d_bout, nreq * sizeof(Key), hipMemcpyDeviceToHost, d.stream));
+        memcpy(d.h_bseg.p, T.segs.data(), nseg * sizeof(BatchSeg));
+        memcpy(d.h_btile0.p, T.req_tile0.data(), (nreq + 1) * sizeof(uint32_t));
+        HIPCHK(hipMemcpyAsync(d.d_bseg.p, d.h_bseg.p, nseg * sizeof(BatchSeg), hipMemcpyHostToDevice, d.stream));
+        HIPCHK(hipMemcpyAsync(d.d_btile0.p, d.h_btile0.p, (nreq + 1) * sizeof(uint32_t), hipMemcpyHostToDevice,
+                              d.stream));
+        HIPCHK(launch(d.f_bscan, L->tiles, kBlock, d.stream, (const BatchSeg*)d.d_bseg.p, (uint32_t)nseg,
+                      d.d_bpart.p));
+        HIPCHK(launch(d.f_breduce, (uint32_t)nreq, kBlock, d.stream, (const Key*)d.d_bpart.p,
+                      (const uint32_t*)d.d_btile0.p, d.d_bout.p));
+        HIPCHK(hipMemcpyAsync(d.h_bout.p, d.d_bout.p, nreq * sizeof(Key), hipMemcpyDeviceToHost, d.stream));
         tiles += L->tiles;
         nonces += T.nonces;
       }
@@ -1076,7 +909,7 @@ int scan_batch_locked(const p1hip_request_t* reqs, size_t n, p1hip_result_t* out
         Dev& d = R.devs[(size_t)L->device];
         HIPCHK(hipStreamSynchronize(d.stream));
         for (size_t r = 0; r < L->reqs.size(); ++r) {
-          const Key kq = finish_key(d.h_bout[r]);
+          const Key kq = finish_key(d.h_bout.p[r]);
           res[L->reqs[r]] = p1hip_result_t{kq.h, kq.n};
         }
       }
@@ -1111,9 +944,89 @@ int scan_batch_locked(const p1hip_request_t* reqs, size_t n, p1hip_result_t* out
   return P1HIP_OK;
 }
 
+// ----------------------------------------------------------------------------
+// p1hip_reduce_pairs
+// ----------------------------------------------------------------------------
+int reduce_pairs_locked(const uint64_t* hashes, const uint64_t* nonces, size_t n, uint64_t* out_hash,
+                        uint64_t* out_nonce) {
+  Runtime& R = rt();
+  std::lock_guard<std::mutex> g(R.mu);
+  int rc = ensure_init(R);
+  if (rc) return rc;
+  Dev& d = R.devs[0];
+  HIPCHK(hipSetDevice(d.ordinal));
+  Key res = {~0ull, ~0ull};
+  if (n > (size_t)kMaxLaunchBlocks * kBlock) return fail(P1HIP_ERR_ARGS, "too many pairs");
+  if (n) {
+    // scratch of exactly this call's size, freed on every exit path (HIPCHK
+    // returns early; the stream is synchronised before the normal one)
+    DevBuf<uint64_t> dh, dn;
+    DevBuf<Key> dp;
+    const uint32_t blocks = (uint32_t)((n + kBlock - 1) / kBlock);
+    HIPCHK(dh.reserve(n, n));
+    HIPCHK(dn.reserve(n, n));
+    HIPCHK(dp.reserve(blocks, blocks));
+    HIPCHK(hipMemcpyAsync(dh.p, hashes, n * 8, hipMemcpyHostToDevice, d.stream));
+    HIPCHK(hipMemcpyAsync(dn.p, nonces, n * 8, hipMemcpyHostToDevice, d.stream));
+    HIPCHK(launch(d.f_pairs, blocks, kBlock, d.stream, (const uint64_t*)dh.p, (const uint64_t*)dn.p, (uint64_t)n,
+                  dp.p));
+    HIPCHK(launch(d.f_reduce, 1, kReduceThreads, d.stream, (const Key*)dp.p, blocks, d.d_res.p));
+    HIPCHK(hipMemcpyAsync(d.h_res.p, d.d_res.p, sizeof(Key), hipMemcpyDeviceToHost, d.stream));
+    HIPCHK(hipStreamSynchronize(d.stream));
+    res = d.h_res.p[0];
+  }
+  res = finish_key(res);
+  *out_hash = res.h;
+  *out_nonce = res.n;
+  return P1HIP_OK;
+}
+
 }  // namespace
 
+// ----------------------------------------------------------------------------
+// C ABI
+// ----------------------------------------------------------------------------
 extern "C" {
+
+int p1hip_init(int want_devices, int* got_devices) {
+  if (got_devices) *got_devices = 0;
+  return guarded([&]() {
+    Runtime& R = rt();
+    std::lock_guard<std::mutex> g(R.mu);
+    int count = 0;
+    if (int rc = device_count(&count)) return rc;
+    int n = want_devices <= 0 ? count : want_devices;
+    if (n > count) return fail(P1HIP_ERR_NO_DEVICE, "asked for more devices than visible");
+    std::vector<int> ords;
+    for (int i = 0; i < n; ++i) ords.push_back(i);
+    int rc = init_locked(R, ords);
+    if (got_devices) *got_devices = rc == 0 ? (int)R.devs.size() : 0;
+    return rc;
+  });
+}
+
+int p1hip_init_devices(const int* ordinals, int n) {
+  if (!ordinals || n <= 0) return fail(P1HIP_ERR_ARGS, "empty device list");
+  return guarded([&]() {
+    Runtime& R = rt();
+    std::lock_guard<std::mutex> g(R.mu);
+    return init_locked(R, std::vector<int>(ordinals, ordinals + n));
+  });
+}
+
+int p1hip_device_count(void) {
+  Runtime& R = rt();
+  std::lock_guard<std::mutex> g(R.mu);
+  return (int)R.devs.size();
+}
+
+int p1hip_scan(const uint8_t* msg, size_t msg_len, uint64_t lower, uint64_t upper, uint64_t* out_hash,
+               uint64_t* out_nonce) {
+  if (!out_hash || !out_nonce) return fail(P1HIP_ERR_ARGS, "null output pointer");
+  if (!msg && msg_len > 0) return fail(P1HIP_ERR_ARGS, "msg == NULL with msg_len > 0");
+  if (msg_len > P1HIP_MAX_MSG_LEN) return fail(P1HIP_ERR_ARGS, "msg_len exceeds P1HIP_MAX_MSG_LEN");
+  return guarded([&]() { return scan_locked(msg, msg_len, lower, upper, out_hash, out_nonce); });
+}
 
 int p1hip_scan_batch(const p1hip_request_t* reqs, size_t n, p1hip_result_t* out) {
   if (n == 0) return P1HIP_OK;
@@ -1133,7 +1046,7 @@ int p1hip_batch_layout(const p1hip_request_t* reqs, size_t n, int ndev, uint32_t
     const int rc = batch_check(reqs, n);
     if (rc) return rc;
     const std::vector<BatchReq> q = batch_reqs(reqs, n);
-    const BatchLayout Y = batch_layout(q.data(), n, ndev, batch_nonce_limit(), batch_tile_limit());
+    const BatchLayout Y = batch_layout(q.data(), n, ndev, knob(kBatchMaxNoncesKnob), knob(kBatchMaxTilesKnob));
     for (size_t i = 0; i < n; ++i) {
       tiles[i] = Y.tiles[i];
       device[i] = Y.device[i];
@@ -1176,53 +1089,6 @@ int p1hip_reduce_pairs(const uint64_t* hashes, const uint64_t* nonces, size_t n,
   if (!out_hash || !out_nonce || (n && (!hashes || !nonces))) return fail(P1HIP_ERR_ARGS, "null pointer");
   return guarded([&]() { return reduce_pairs_locked(hashes, nonces, n, out_hash, out_nonce); });
 }
-
-}  // extern "C"
-
-namespace {
-int reduce_pairs_locked(const uint64_t* hashes, const uint64_t* nonces, size_t n, uint64_t* out_hash,
-                        uint64_t* out_nonce) {
-  Runtime& R = rt();
-  std::lock_guard<std::mutex> g(R.mu);
-  int rc = ensure_init(R);
-  if (rc) return rc;
-  Dev& d = R.devs[0];
-  HIPCHK(hipSetDevice(d.ordinal));
-  Key res = {~0ull, ~0ull};
-  if (n > (size_t)kMaxLaunchBlocks * kBlock) return fail(P1HIP_ERR_ARGS, "too many pairs");
-  if (n) {
-    uint64_t *dh = nullptr, *dn = nullptr;
-    Key* dp = nullptr;
-    // frees the scratch buffers on every exit path (HIPCHK returns early)
-    struct Scratch {
-      uint64_t **a, **b;
-      Key** c;
-      ~Scratch() {
-        if (*a) (void)hipFree(*a);
-        if (*b) (void)hipFree(*b);
-        if (*c) (void)hipFree(*c);
-      }
-    } scratch{&dh, &dn, &dp};
-    const uint32_t blocks = (uint32_t)((n + kBlock - 1) / kBlock);
-    HIPCHK(hipMalloc(&dh, n * 8));
-    HIPCHK(hipMalloc(&dn, n * 8));
-    HIPCHK(hipMalloc(&dp, (size_t)blocks * sizeof(Key)));
-    HIPCHK(hipMemcpyAsync(dh, hashes, n * 8, hipMemcpyHostToDevice, d.stream));
-    HIPCHK(hipMemcpyAsync(dn, nonces, n * 8, hipMemcpyHostToDevice, d.stream));
-    HIPCHK(launch(d.f_pairs, blocks, kBlock, d.stream, (const uint64_t*)dh, (const uint64_t*)dn, (uint64_t)n, dp));
-    HIPCHK(launch(d.f_reduce, 1, kReduceThreads, d.stream, (const Key*)dp, blocks, d.d_res));
-    HIPCHK(hipMemcpyAsync(d.h_res, d.d_res, sizeof(Key), hipMemcpyDeviceToHost, d.stream));
-    HIPCHK(hipStreamSynchronize(d.stream));
-    res = d.h_res[0];
-  }
-  res = finish_key(res);
-  *out_hash = res.h;
-  *out_nonce = res.n;
-  return P1HIP_OK;
-}
-}  // namespace
-
-extern "C" {
 
 int p1hip_set_profiling(int on) {
   Runtime& R = rt();
@@ -1292,14 +1158,15 @@ const char* p1hip_test_knobs(void) {
     std::vector<std::pair<std::string, std::string>> kv;
     if (test_knobs_on()) {
       kv.push_back({"P1HIP_TEST_KNOBS", "1"});
-      for (const char* k : kTestKnobs)
-        if (const char* v = test_knob(k)) kv.push_back({k, v});
+      for (const Knob& K : kKnobs)
+        if (const char* v = test_knob(K.name)) kv.push_back({K.name, v});
     }
     // ... and the ones read at init that the open devices still run with,
     // even if the environment has changed since
     Runtime& R = rt();
     std::lock_guard<std::mutex> g(R.mu);
-    auto add = [&](const char* k, const std::string& v) {
+    auto add = [&](KnobId id, const std::string& v) {
+      const char* k = kKnobs[id].name;
       for (auto& e : kv)
         if (e.first == k) {
           if (e.second != v) e.second += " (init: " + v + ")";
@@ -1308,12 +1175,12 @@ const char* p1hip_test_knobs(void) {
       kv.push_back({k, "(init: " + v + ")"});
     };
     if (!R.devs.empty()) {
-      if (R.min_fast_threads != kMinFastThreads) add("P1HIP_MIN_FAST_THREADS", std::to_string(R.min_fast_threads));
-      if (R.fail_device >= 0) add("P1HIP_TEST_FAIL_DEVICE", std::to_string(R.fail_device));
-      if (!R.tabulate) add("P1HIP_NO_TABLE", "1");
-      if (!R.split) add("P1HIP_NO_SPLIT", "1");
-      if (!R.use_rccl) add("P1HIP_NO_RCCL", "1");
-      if (R.rccl_one) add("P1HIP_FORCE_RCCL", "1");
+      if (R.min_fast_threads != kMinFastThreads) add(kMinFastThreadsKnob, std::to_string(R.min_fast_threads));
+      if (R.fail_device >= 0) add(kTestFailDeviceKnob, std::to_string(R.fail_device));
+      if (!R.tabulate) add(kNoTableKnob, "1");
+      if (!R.split) add(kNoSplitKnob, "1");
+      if (!R.use_rccl) add(kNoRcclKnob, "1");
+      if (R.rccl_one) add(kForceRcclKnob, "1");
     }
     for (size_t i = 0; i < kv.size(); ++i) s += (i ? ";" : "") + kv[i].first + "=" + kv[i].second;
   } catch (...) {

@@ -46,6 +46,30 @@ def test_many_launches_per_scan_keep_every_tile(gpu, monkeypatch):
     assert gpu.scan(*C2) == C2_MIN
 
 
+def test_segment_tables_regrow_and_are_kept(gpu, oracle_mod, monkeypatch):
+    """One workgroup per launch: "bradfitz" [1, 200000] needs more launch
+    slots than the segment tables' first allocation of 4, so they are freed
+    and regrown before the first launch; the next scan runs one launch on the
+    kept, larger buffers, and a scan of configs[0]'s range follows."""
+    want = oracle_mod.scan(b"bradfitz", 1, 200000, threads=8)
+    monkeypatch.setenv("P1HIP_MAX_LAUNCH_BLOCKS", "1")
+    try:
+        gpu.reset_stats()
+        assert gpu.scan(b"bradfitz", 1, 200000) == want
+        assert gpu.get_stats()["scan_launches"] >= 5
+    finally:
+        monkeypatch.delenv("P1HIP_MAX_LAUNCH_BLOCKS")
+    gpu.reset_stats()
+    assert gpu.scan(b"bradfitz", 1, 200000) == want
+    assert gpu.get_stats()["scan_launches"] == 1
+    monkeypatch.setenv("P1HIP_SMALL_MAX_NONCES", str(1 << 16))  # the session runs with the small path off
+    try:
+        assert gpu.scan(b"bradfitz", 0, 9999) == (1419516646206828, 9898)
+        assert gpu.get_stats()["small_scans"] == 1
+    finally:
+        monkeypatch.setenv("P1HIP_SMALL_MAX_NONCES", "0")
+
+
 def test_small_and_queued_scans_interleave(gpu, oracle_mod):
     """Scans below one grid (no queue: one tile per workgroup) between
     queued ones, checked against the oracle."""

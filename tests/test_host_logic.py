@@ -29,6 +29,21 @@ def emu(msg, lo, hi, generic=False, minthreads=None, nosplit=False, variants=Non
     return (int(out[0]), int(out[1])), int(out[2]), int(out[3])
 
 
+def emu_packed(msg, lo, hi, mode, minthreads=None, variants=None):
+    """p1emu's device-order replays: mode "packed=MAXBLOCKS[,MAXSEGS]" (the
+    library's launch packing and segment tables, k_scan tile by tile) or
+    "small" (k_scan_small's argument block).  -> (key, launches, tiles, segs)"""
+    args = [EMU, msg.hex() if msg else "-", str(lo), str(hi)]
+    if minthreads is not None:
+        args.append(f"minthreads={minthreads}")
+    r = subprocess.run(args + [mode], capture_output=True, text=True, check=True)
+    out = r.stdout.split()
+    if variants is not None and out[4] != "-":
+        variants.update(tuple(int(x) for x in v.split(":")) for v in out[4].split(","))
+    n = re.fullmatch(r"launches=(\d+) tiles=(\d+) segs=(\d+)", r.stderr.strip())
+    return (int(out[0]), int(out[1])), int(n.group(1)), int(n.group(2)), int(n.group(3))
+
+
 def all_variants(plain_mode2):
     """(FV, MODE, TRAIL) of every P1_CASE in fast_variants.inc; the mode-2
     block is compiled only with -DP1_NV2_PLAIN (p1emu is)."""
@@ -210,6 +225,86 @@ def test_emu_range_top(oracle_mod):
 def test_emu_empty_range():
     got, nf, ng = emu(b"bradfitz", 10, 9)
     assert got == (U64_MAX, 0) and nf == 0 and ng == 0
+
+
+BRADFITZ_200K = (85364550342847, 98985)  # the oracle's answer for "bradfitz" [1, 200000]
+
+
+@pytest.mark.parametrize("minthreads,nfast,ngen", [(None, 5, 2), (1, 3, 4)], ids=["floor", "k3"])
+def test_emu_packed_launches(oracle_mod, minthreads, nfast, ngen):
+    """The library's launch packing (scan_pack.hpp) replayed the way the
+    device runs it: "bradfitz" [1, 200000] plans 7 pieces; whatever the
+    per-launch workgroup and segment caps cut them into, every tile is run
+    once and the fold of the partials is the oracle's answer."""
+    m = b"bradfitz"
+    assert oracle_mod.scan(m, 1, 200000, threads=8) == BRADFITZ_200K
+    plain, nf, ng = emu(m, 1, 200000, minthreads=minthreads)
+    assert plain == BRADFITZ_200K and (nf, ng) == (nfast, ngen)
+    runs = {mode: emu_packed(m, 1, 200000, mode, minthreads=minthreads)
+            for mode in ("packed=1", "packed=3", "packed=0", "packed=0,2", "packed=3,2")}
+    for mode, (key, launches, tiles, segs) in runs.items():
+        print(mode, key, launches, tiles, segs)
+        assert key == plain == BRADFITZ_200K, mode
+        assert segs == 7, mode  # every piece is in exactly one segment table
+    assert runs["packed=1"][1] == 7       # one launch per piece
+    assert runs["packed=0"][1] == 1       # the library's limits: one launch
+    assert runs["packed=0,2"][1] >= 4     # 7 pieces, 2 segments per launch
+    assert runs["packed=3,2"][1] >= 4
+    assert runs["packed=1"][1] >= runs["packed=3"][1] >= 1
+    # p1emu itself refuses a packing whose tiles are not the plan's
+    # total_blocks; here: the same count however the plan is cut
+    assert len({r[2] for r in runs.values()}) == 1 and runs["packed=0"][2] >= 7
+
+
+def test_emu_packed_table_layouts(oracle_mod):
+    """MODE 5 / MODE 7 pieces (K+W table pointer in the segment) through the
+    packing at 2 workgroups per launch: the layouts of
+    test_emu_every_layout_k3 (its message lengths and ranges) with q = 64..68
+    (MODE 7: one digit in tail block 1, q = 64; MODE 5: 2 to 5 digits).
+    The pieces are reordered before they are cut into launches, so a table
+    pointer taken by position instead of by plan index gives a wrong hash."""
+    import concurrent.futures as cf
+
+    rnd = random.Random(8)
+    cases = []
+    for L in range(0, 128):  # the same stream of messages and ranges as test_emu_every_layout_k3
+        m = bytes(rnd.randrange(32, 127) for _ in range(L))
+        for d in (4, 5, 9, 10, 11, 12, 20):
+            b = 10 ** (d - 1)
+            lo = b + rnd.randrange(0, 3000 if d == 4 else 10**4) if d < 20 else b
+            q = (L + 1) % 64 + d - 1
+            hi = min(lo + {67: 24999, 68: 219999}.get(q, 4999), U64_MAX)
+            if 64 <= q <= 68:
+                cases.append((m, lo, hi))
+
+    def run(c):
+        m, lo, hi = c
+        seen = set()
+        key, _, _, segs = emu_packed(m, lo, hi, "packed=2", minthreads=1, variants=seen)
+        return {v[1] for v in seen} & {5, 7}, key == oracle_mod.scan(m, lo, hi, threads=1), segs, c
+
+    with cf.ThreadPoolExecutor(8) as ex:
+        res = list(ex.map(run, cases))
+    bad = [c for _, ok, _, c in res if not ok]
+    assert not bad, bad[:3]
+    tabled = [(modes, segs) for modes, _, segs, _ in res if modes]
+    print(len(cases), "cases,", len(tabled), "with a table piece; segments:", sorted(s for _, s in tabled))
+    # residues r = (L + 1) % 64 < 64 with r + d - 1 in 64..68: 3 for d = 4, 4
+    # for d = 5, 5 for the other five digit counts; 2 lengths each.  Below
+    # d = 20 the range starts off a block boundary, so the tabulated piece
+    # shares its plan with ragged generic edges that the packing orders after it
+    assert len(cases) == 2 * (3 + 4 + 5 * 5) and set().union(*(modes for modes, _ in tabled)) == {5, 7}
+    assert sum(1 for _, segs in tabled if segs >= 2) >= len(tabled) // 2
+
+
+@pytest.mark.parametrize("lo,hi,tiles,segs", [(1000, 1000, 1, 1), (1000, 1255, 1, 1), (1000, 1256, 2, 1),
+                                              (0, 65535, 259, 5), (95, 12000, 1 + 4 + 36 + 8, 4)])
+def test_emu_small_args(oracle_mod, lo, hi, tiles, segs):
+    """k_scan_small replayed from the library's argument block (scan_pack.hpp
+    fill_small): 1, 256, 257 and 2^16 nonces, and a range over four decades
+    (one generic piece per decade, ceil(nonces / 256) tiles each)."""
+    got = emu_packed(b"bradfitz", lo, hi, "small")
+    assert got == (oracle_mod.scan(b"bradfitz", lo, hi, threads=8), 1, tiles, segs)
 
 
 def _header_symbols():

@@ -3,11 +3,13 @@
 // one simulated GPU thread at a time, and prints the (hash, nonce) result.
 //
 // It exists so the layout logic (decade split, digit placement, lo-digit
-// deltas, PRE/TRAIL blocks) can be parity-tested against the oracle in the
+// deltas, PRE/TRAIL blocks) and the launch packing (piece order, launch cuts,
+// segment tables, block0) can be parity-tested against the oracle in the
 // CPU-only test suite.  It is never part of libp1hip.so and never used to
 // produce a product result.
 //
 // usage: p1emu <msg-hex> <lower> <upper> [generic | minthreads=N] [nosplit] [notable]
+//              [packed=MAXBLOCKS[,MAXSEGS] | small]
 //   minthreads=N sets the planner's occupancy floor (1 keeps k = 3 on small
 //   ranges, so every k = 3 variant is replayed); nosplit uses mode 2 for
 //   straddling lo digits (p1emu is built with -DP1_NV2_PLAIN); notable keeps
@@ -15,6 +17,17 @@
 //   prints "<hash> <nonce> <fast_launches> <generic_launches> <variants>"
 //   where <variants> lists the fast variants run as FV:MODE:TRAIL,... ("-"
 //   when none)
+//
+//   Without packed= or small the plan's pieces are replayed one at a time.
+//   packed=MAXBLOCKS[,MAXSEGS] replays the scan the way the device runs it:
+//   the library's own packing (p1_amd/csrc/scan_pack.hpp pack_scan, at most
+//   MAXBLOCKS workgroups and MAXSEGS segments per launch; 0 or nothing = the
+//   library's limits) and segment tables (fill_segments), then k_scan tile by
+//   tile: the kernel's segment walk, the variant chosen from the segment's
+//   kind, kBlock threads, one partial per tile, all partials folded.
+//   small replays k_scan_small from the library's argument block (fill_small;
+//   generic pieces, at most 2^16 nonces).  Both also print
+//   "launches=<n> tiles=<n> segs=<n>" on stderr.
 #include <inttypes.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -23,7 +36,7 @@
 #include <string>
 #include <vector>
 
-#include "../p1_amd/csrc/planner.hpp"
+#include "../p1_amd/csrc/scan_pack.hpp"
 
 using namespace p1;
 
@@ -52,6 +65,33 @@ static Key dispatch_fast(const Launch& L0) {
   exit(3);
 }
 
+// One tile of k_scan: the workgroup's kBlock threads and their minimum.  The
+// segment walk is p1emu's own copy of the two lines in p1hip_kernels.hip
+// scan_tile (the kernel source is not shared with the host).
+static Key scan_tile(const Segment* segs, uint32_t nseg, uint32_t b) {
+  uint32_t si = 0;
+  while (si + 1 < nseg && segs[si + 1].block0 <= b) ++si;
+  const Segment& S = segs[si];
+  Key m = {~0ull, ~0ull};
+  for (uint32_t t = 0; t < (uint32_t)kBlock; ++t) {
+    const uint32_t local = (b - S.block0) * kBlock + t;
+    Key k;
+    switch (S.kind) {
+#define P1_CASE(FV, NV, TR)                   \
+  case variant_id(FV, NV, TR):                \
+    k = fast_thread<FV, NV, TR>(S.fa, local); \
+    break;
+#include "../p1_amd/csrc/fast_variants.inc"
+#undef P1_CASE
+      default:
+        k = generic_thread(S.ga, local);
+        break;
+    }
+    if (key_lt(k, m)) m = k;
+  }
+  return m;
+}
+
 static std::vector<uint8_t> unhex(const char* s) {
   std::vector<uint8_t> v;
   size_t n = strlen(s);
@@ -65,23 +105,39 @@ static std::vector<uint8_t> unhex(const char* s) {
 
 int main(int argc, char** argv) {
   if (argc < 4) {
-    fprintf(stderr, "usage: %s <msg-hex|-> <lower> <upper> [generic|minthreads=N]\n", argv[0]);
+    fprintf(stderr,
+            "usage: %s <msg-hex|-> <lower> <upper> [generic|minthreads=N] [nosplit] [notable] "
+            "[packed=MAXBLOCKS[,MAXSEGS]|small]\n",
+            argv[0]);
     return 2;
   }
   std::vector<uint8_t> msg = strcmp(argv[1], "-") == 0 ? std::vector<uint8_t>() : unhex(argv[1]);
   const uint64_t lower = strtoull(argv[2], nullptr, 10);
   const uint64_t upper = strtoull(argv[3], nullptr, 10);
-  const bool generic_only = argc > 4 && strcmp(argv[4], "generic") == 0;
+  bool generic_only = argc > 4 && strcmp(argv[4], "generic") == 0;
   uint64_t min_threads = kMinFastThreads;
-  bool split = true, tabulate = true;
+  bool split = true, tabulate = true, packed = false, small = false;
+  uint64_t max_blocks = kMaxLaunchBlocks;
+  uint32_t max_segs = kMaxSegs;
   for (int i = 4; i < argc; ++i) {
     if (strncmp(argv[i], "minthreads=", 11) == 0) min_threads = strtoull(argv[i] + 11, nullptr, 10);
     if (strcmp(argv[i], "nosplit") == 0) split = false;
     if (strcmp(argv[i], "notable") == 0) tabulate = false;
+    if (strcmp(argv[i], "small") == 0) small = generic_only = true;  // as run_small plans
+    if (strncmp(argv[i], "packed=", 7) == 0) {
+      packed = true;
+      char* end = nullptr;
+      const uint64_t mb = strtoull(argv[i] + 7, &end, 10);
+      const uint64_t ms = *end == ',' ? strtoull(end + 1, nullptr, 10) : 0;
+      if (mb > 0 && mb < kMaxLaunchBlocks) max_blocks = mb;
+      if (ms > 0 && ms < kMaxSegs) max_segs = (uint32_t)ms;
+    }
   }
   Key best = {~0ull, ~0ull};
   int nf = 0, ng = 0;
   std::string vars;
+  size_t launches = 0;
+  uint64_t tiles = 0, nsegs = 0;
   if (lower <= upper) {
     Plan plan;
     std::string err = make_plan(msg.data(), msg.size(), lower, upper, plan, !generic_only, min_threads, split, tabulate);
@@ -90,25 +146,91 @@ int main(int argc, char** argv) {
       return 1;
     }
     for (const Launch& L : plan.launches) {
-      Key k;
       if (L.fast) {
         ++nf;
-        k = dispatch_fast(L);
         char v[32];
         snprintf(v, sizeof v, "%s%d:%d:%d", vars.empty() ? "" : ",", L.fv, L.mode, (int)L.trail);
         vars += v;
       } else {
         ++ng;
-        k = {~0ull, ~0ull};
-        for (uint64_t g = 0; g < L.threads; ++g) {
-          Key t = generic_thread(L.ga, g);
-          if (key_lt(t, k)) k = t;
-        }
       }
-      if (key_lt(k, best)) best = k;
+    }
+    ScanCounters ctr;
+    if (small) {
+      // k_scan_small: grid = a.nblocks workgroups, pieces found by the walk
+      // over a.block0 (p1emu's copy of the kernel's), the last workgroup's
+      // fold of the partials
+      SmallArgs a;
+      err = fill_small(plan, a, ctr);
+      if (!err.empty()) {
+        fprintf(stderr, "small error: %s\n", err.c_str());
+        return 1;
+      }
+      std::vector<Key> part(a.nblocks);
+      for (uint32_t b = 0; b < a.nblocks; ++b) {
+        uint32_t si = 0;
+        while (si + 1 < a.nseg && a.block0[si + 1] <= b) ++si;
+        Key m = {~0ull, ~0ull};
+        for (uint32_t t = 0; t < (uint32_t)kBlock; ++t) {
+          const Key k = generic_thread(a.ga[si], (uint64_t)(b - a.block0[si]) * kBlock + t);
+          if (key_lt(k, m)) m = k;
+        }
+        part[b] = m;
+      }
+      for (const Key& p : part)
+        if (key_lt(p, best)) best = p;
+      launches = 1;
+      tiles = a.nblocks;
+      nsegs = a.nseg;
+    } else if (packed) {
+      // K+W tables in host memory, one per MODE 5 / 7 piece, by plan index
+      std::vector<std::vector<uint32_t>> tabs(plan.launches.size());
+      std::vector<uint64_t> tabptr(plan.launches.size(), 0);
+      for (size_t i = 0; i < plan.launches.size(); ++i) {
+        const Launch& L = plan.launches[i];
+        if (!L.fast || (L.mode != 5 && L.mode != 7)) continue;
+        tabs[i] = build_kwtable(L);
+        tabptr[i] = (uint64_t)(uintptr_t)tabs[i].data();
+      }
+      const ScanPack P = pack_scan(plan, max_blocks, max_segs);
+      std::vector<Segment> segs(max_segs);
+      std::vector<Key> part;  // one partial per tile, all launches (k_reduce folds them)
+      for (const ScanBatch& B : P.batches) {
+        err = fill_segments(plan, P, B, tabptr.data(), segs.data(), ctr);
+        if (!err.empty()) {
+          fprintf(stderr, "segment error: %s\n", err.c_str());
+          return 1;
+        }
+        for (uint32_t b = 0; b < B.blocks; ++b) part.push_back(scan_tile(segs.data(), (uint32_t)B.count, b));
+        nsegs += B.count;
+      }
+      if (part.size() != plan.total_blocks || P.total_blocks != plan.total_blocks) {
+        fprintf(stderr, "packing error: %zu tiles replayed, %u packed, %u planned\n", part.size(), P.total_blocks,
+                plan.total_blocks);
+        return 1;
+      }
+      for (const Key& p : part)
+        if (key_lt(p, best)) best = p;
+      launches = P.batches.size();
+      tiles = part.size();
+    } else {
+      for (const Launch& L : plan.launches) {
+        Key k;
+        if (L.fast) {
+          k = dispatch_fast(L);
+        } else {
+          k = {~0ull, ~0ull};
+          for (uint64_t g = 0; g < L.threads; ++g) {
+            Key t = generic_thread(L.ga, g);
+            if (key_lt(t, k)) k = t;
+          }
+        }
+        if (key_lt(k, best)) best = k;
+      }
     }
   }
   if (best.h == ~0ull) best.n = 0;  // identity of miner.go:56
   printf("%" PRIu64 " %" PRIu64 " %d %d %s\n", best.h, best.n, nf, ng, vars.empty() ? "-" : vars.c_str());
+  if (packed || small) fprintf(stderr, "launches=%zu tiles=%" PRIu64 " segs=%" PRIu64 "\n", launches, tiles, nsegs);
   return 0;
 }
