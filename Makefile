@@ -5,7 +5,7 @@ HIPFLAGS ?= -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -Wall
 LLVM ?= /opt/rocm/lib/llvm/bin
 CSRC := p1_amd/csrc
 HDRS := $(CSRC)/sha256_dev.hpp $(CSRC)/scan_core.hpp $(CSRC)/planner.hpp $(CSRC)/fast_variants.inc $(CSRC)/variant_cost.inc \
-        $(CSRC)/scan_abi.hpp $(CSRC)/scan_pack.hpp $(CSRC)/argmin_dev.hpp $(CSRC)/batch_abi.hpp $(CSRC)/batch_plan.hpp include/p1hip.h
+        $(CSRC)/scan_abi.hpp $(CSRC)/scan_pack.hpp $(CSRC)/argmin_dev.hpp $(CSRC)/batch_abi.hpp $(CSRC)/batch_plan.hpp $(CSRC)/wide_plan.hpp include/p1hip.h
 # what the device code includes (the host-side planner does not rebuild it)
 DEVHDRS := $(CSRC)/sha256_dev.hpp $(CSRC)/scan_core.hpp $(CSRC)/fast_variants.inc $(CSRC)/scan_abi.hpp $(CSRC)/argmin_dev.hpp
 # device code: HIP C++ -> gfx950 assembly -> tools/isa_post.py post-pass
@@ -129,13 +129,15 @@ tools/vbank: tools/vbank.hip
 
 # host-only replay of the kernels' per-thread code and of the library's launch
 # packing (layout and segment-table tests; not product)
-tools/p1emu: tools/p1emu.cpp $(HDRS)
+tools/p1emu: tools/p1emu.cpp tools/scan_replay.hpp $(HDRS)
 	$(HIPCC) -O2 -std=c++17 -DP1_NV2_PLAIN -o $@ tools/p1emu.cpp
 
 # host-only replay of a p1hip_scan_batch call: the library's own table builder
-# and segment lookup, generic_thread per thread, the per-request fold
-tools/batch_emu: tools/batch_emu.cpp $(HDRS)
-	$(HIPCC) -O2 -std=c++17 -o $@ tools/batch_emu.cpp
+# and segment lookup, generic_thread per thread, the per-request fold; and
+# (`batch_emu wide`) of a p1hip_scan_batch_wide call: the library's own
+# wide_plan.hpp, k_scan tile by tile, the range fold
+tools/batch_emu: tools/batch_emu.cpp tools/scan_replay.hpp $(HDRS)
+	$(HIPCC) -O2 -std=c++17 -pthread -o $@ tools/batch_emu.cpp
 
 oracle:
 	$(MAKE) -C oracle
@@ -208,14 +210,14 @@ $(SANLIB)/tsan/capi_san_stress: tests/capi_san_stress.cpp include/p1hip.h $(SANL
 	$(SANCXX) $(SANBASE) $(SAN_tsan) -Iinclude -o $@ tests/capi_san_stress.cpp -L$(SANLIB)/tsan -lp1hip \
 	    -Wl,-rpath,'$$ORIGIN' -Loracle -lp1oracle -Wl,-rpath,'$$ORIGIN/../../../oracle'
 
-$(SANDIR)/asan/p1emu: tools/p1emu.cpp $(HDRS)
+$(SANDIR)/asan/p1emu: tools/p1emu.cpp tools/scan_replay.hpp $(HDRS)
 	mkdir -p $(@D)
 	$(HIPCC) -O1 -g -std=c++17 -fno-omit-frame-pointer -Xarch_host -fsanitize=address -Xarch_host -fsanitize=undefined \
 	    -Xarch_host -fno-sanitize-recover=undefined -DP1_NV2_PLAIN -o $@ tools/p1emu.cpp
 
-$(SANDIR)/asan/batch_emu: tools/batch_emu.cpp $(HDRS)
+$(SANDIR)/asan/batch_emu: tools/batch_emu.cpp tools/scan_replay.hpp $(HDRS)
 	mkdir -p $(@D)
-	$(HIPCC) -O1 -g -std=c++17 -fno-omit-frame-pointer -Xarch_host -fsanitize=address -Xarch_host -fsanitize=undefined \
+	$(HIPCC) -O1 -g -std=c++17 -pthread -fno-omit-frame-pointer -Xarch_host -fsanitize=address -Xarch_host -fsanitize=undefined \
 	    -Xarch_host -fno-sanitize-recover=undefined -o $@ tools/batch_emu.cpp
 
 # libFuzzer harness of the wire codecs (tests/fuzz/fuzz_codecs.cpp) with

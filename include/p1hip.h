@@ -142,6 +142,70 @@ typedef struct {
 } p1hip_batch_stats_t;
 int p1hip_get_batch_stats(p1hip_batch_stats_t *out);   /* cleared by p1hip_reset_stats */
 
+/* Many requests in one call, mid-size ones included.  p1hip_scan_batch runs
+ * every request above 2^16 nonces alone, but a job of 10^5..10^7 nonces (the
+ * reference's own job size) is a handful of k_scan segments and a few dozen
+ * workgroups on a device that holds about a thousand.  Here the requests
+ * above 2^16 and of at most 2^24 nonces -- of any messages -- share k_scan
+ * launches, up to 64 segments each; their ragged edges share one k_batch_scan
+ * launch; k_wide_reduce folds one result per request; one copy back and one
+ * stream synchronisation per device end the call.  Each request takes one
+ * route (p1hip_wide_layout reports it):
+ *   0 empty range (answered on the host)
+ *   1 small: at most 2^16 nonces, p1hip_scan_batch's coalesced launch pair
+ *   2 wide:  above that and at most 2^24 nonces, shared k_scan launches
+ *   3 individual: larger, one by one through the p1hip_scan path
+ * The contract is p1hip_scan_batch's: out[i] is exactly what
+ * p1hip_scan(reqs[i]...) returns; every request is validated before anything
+ * runs (P1HIP_ERR_ARGS names the index) and `out` is untouched on any error;
+ * n == 0 returns 0 without opening a device.  With several devices the wide
+ * requests are cut, in request order, into contiguous groups of near-equal
+ * predicted cost, one per device (a request lives wholly on one device), all
+ * enqueued before any stream is synchronised. */
+int p1hip_scan_batch_wide(const p1hip_request_t *reqs, size_t n, p1hip_result_t *out);
+
+/* Host only (no device): how p1hip_scan_batch_wide would lay the call out
+ * over ndev devices.  route[i]: as above; device[i]: the device of a wide
+ * request (-1 otherwise); segs[i]: the k_scan segments of a wide request (its
+ * fast pieces) and tiles[i]: all its workgroup tiles (both 0 otherwise).  A
+ * wide request is planned with an occupancy floor of 2^18 / min(wide requests
+ * on its device, 64) threads, so the more requests share the launches, the
+ * more nonces each thread runs (10^k, k = 1..3) and the fewer tiles a request
+ * has: tiles[i] shows the k chosen. */
+int p1hip_wide_layout(const p1hip_request_t *reqs, size_t n, int ndev,
+                      int32_t *route, int32_t *device, uint32_t *segs, uint32_t *tiles);
+
+/* Host only: the range table of the same layout, for tests and tools.  A
+ * range is a run of tiles of one request in its device's partial array:
+ * tiles [tile0[j], tile0[j] + ntiles[j]) of request req[j], written by k_scan
+ * launch launch[j] of that device (from 0; -1: the device's k_batch_scan
+ * launch of the generic pieces).  Ranges are listed by device, then request.
+ * *count receives the number of ranges; only the first `cap` are written.
+ * dev_tiles[d] (ndev entries) is the size of device d's partial array. */
+int p1hip_wide_ranges(const p1hip_request_t *reqs, size_t n, int ndev, size_t cap, size_t *count,
+                      uint32_t *req, uint32_t *tile0, uint32_t *ntiles, int32_t *launch,
+                      uint32_t *dev_tiles);
+
+/* Accounting of p1hip_scan_batch_wide since p1hip_reset_stats.  Its small
+ * requests also count, as one p1hip_scan_batch call, in p1hip_batch_stats_t,
+ * its individual ones in p1hip_stats_t as scans; wide ones only here. */
+typedef struct {
+  uint64_t calls;            /* p1hip_scan_batch_wide calls that succeeded        */
+  uint64_t requests;         /* requests in them                                  */
+  uint64_t empty;            /* ... per route: lower > upper                      */
+  uint64_t small;            /*     at most 2^16 nonces                           */
+  uint64_t wide;             /*     sharing k_scan launches                       */
+  uint64_t individual;       /*     run one by one                                */
+  uint64_t scan_launches;    /* k_scan launches of the wide route                 */
+  uint64_t scan_segments;    /* segments in their tables (fast pieces)            */
+  uint64_t generic_launches; /* k_batch_scan launches of the wide route           */
+  uint64_t generic_segments; /* generic pieces in their tables                    */
+  uint64_t tiles;            /* workgroup tiles of the wide route                 */
+  uint64_t nonces;           /* nonces they hashed                                */
+  double wall_ms;            /* host wall time inside p1hip_scan_batch_wide       */
+} p1hip_wide_stats_t;
+int p1hip_get_wide_stats(p1hip_wide_stats_t *out);     /* cleared by p1hip_reset_stats */
+
 /* Kernel-level accounting.  One p1hip_scan = one (rarely several) launch of
  * the scan kernel k_scan per device, covering every decade of the range; a
  * share of at most 2^16 nonces is one launch of k_scan_small instead (plan in
@@ -227,7 +291,10 @@ int p1hip_comm_info(int index, int *nranks, int *rank);
  * removed from p1hip_stats_t, so the fields after fast_alg_ops moved); 5 =
  * p1hip 0.5 (p1hip_comm_info and this query added; the structs are as in 4);
  * 6 = p1hip 0.6 (p1hip_scan_batch, p1hip_batch_layout, p1hip_get_batch_stats
- * and their structs added; no existing struct changed). */
+ * and their structs added; no existing struct changed).  Still 6 with
+ * p1hip_scan_batch_wide, p1hip_wide_layout, p1hip_wide_ranges,
+ * p1hip_get_wide_stats and p1hip_wide_stats_t: purely additive, the layout of
+ * every existing struct is unchanged. */
 #define P1HIP_ABI_VERSION 6
 int p1hip_abi_version(void);
 

@@ -17,6 +17,9 @@ from ._lib import (  # noqa: F401
     scan_batch,
     batch_layout,
     get_batch_stats,
+    scan_batch_wide,
+    wide_layout,
+    get_wide_stats,
     hash,
     reduce_pairs,
     plan_shards,

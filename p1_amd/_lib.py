@@ -88,6 +88,27 @@ class BatchStats(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class WideStats(ctypes.Structure):
+    _fields_ = [
+        ("calls", U64),
+        ("requests", U64),
+        ("empty", U64),
+        ("small", U64),
+        ("wide", U64),
+        ("individual", U64),
+        ("scan_launches", U64),
+        ("scan_segments", U64),
+        ("generic_launches", U64),
+        ("generic_segments", U64),
+        ("tiles", U64),
+        ("nonces", U64),
+        ("wall_ms", ctypes.c_double),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class DeviceInfo(ctypes.Structure):
     _fields_ = [
         ("ordinal", ctypes.c_int32),
@@ -123,6 +144,15 @@ SIGNATURES = [
      [ctypes.POINTER(Request), ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(ctypes.c_uint32),
       ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
     ("p1hip_get_batch_stats", ctypes.c_int, [ctypes.POINTER(BatchStats)]),
+    ("p1hip_scan_batch_wide", ctypes.c_int, [ctypes.POINTER(Request), ctypes.c_size_t, ctypes.POINTER(Result)]),
+    ("p1hip_wide_layout", ctypes.c_int,
+     [ctypes.POINTER(Request), ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(ctypes.c_int32),
+      ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]),
+    ("p1hip_wide_ranges", ctypes.c_int,
+     [ctypes.POINTER(Request), ctypes.c_size_t, ctypes.c_int, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t),
+      ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32),
+      ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_uint32)]),
+    ("p1hip_get_wide_stats", ctypes.c_int, [ctypes.POINTER(WideStats)]),
     ("p1hip_hash", ctypes.c_int, [ctypes.c_char_p, ctypes.c_size_t, U64, ctypes.POINTER(U64)]),
     ("p1hip_plan_shards", ctypes.c_int,
      [ctypes.c_char_p, ctypes.c_size_t, U64, U64, ctypes.c_int, ctypes.POINTER(U64), ctypes.POINTER(U64)]),
@@ -232,6 +262,52 @@ def get_batch_stats():
     """Accounting of scan_batch since reset_stats (p1hip_get_batch_stats)."""
     s = BatchStats()
     _check(load().p1hip_get_batch_stats(ctypes.byref(s)))
+    return s.as_dict()
+
+
+WIDE_ROUTES = ("empty", "small", "wide", "individual")
+
+
+def scan_batch_wide(requests):
+    """p1hip_scan_batch_wide: as scan_batch, and the requests above 2^16 and
+    of at most 2^24 nonces share k_scan launches instead of running alone."""
+    arr, rows = _requests(requests)
+    out = (Result * max(len(rows), 1))()
+    _check(load().p1hip_scan_batch_wide(arr, len(rows), out))
+    return [(out[i].hash, out[i].nonce) for i in range(len(rows))]
+
+
+def wide_layout(requests, ndev):
+    """p1hip_wide_layout + p1hip_wide_ranges: how scan_batch_wide would lay
+    `requests` out over `ndev` devices.  Returns (per request {"route" (one
+    of WIDE_ROUTES), "device", "segs", "tiles", "ranges": [(tile0, ntiles,
+    launch)]}, [tiles of each device's partial array]); a range's launch is
+    the device's k_scan launch that writes it, -1 for the generic tiles.
+    Host-only."""
+    arr, rows = _requests(requests)
+    n = len(rows)
+    route, device = (ctypes.c_int32 * max(n, 1))(), (ctypes.c_int32 * max(n, 1))()
+    segs, tiles = (ctypes.c_uint32 * max(n, 1))(), (ctypes.c_uint32 * max(n, 1))()
+    _check(load().p1hip_wide_layout(arr, n, int(ndev), route, device, segs, tiles))
+    lay = [{"route": WIDE_ROUTES[route[i]], "device": device[i], "segs": segs[i], "tiles": tiles[i], "ranges": []}
+           for i in range(n)]
+    cap = sum(x["segs"] + 1 for x in lay)  # one range per segment, one for the generic tiles
+    count = ctypes.c_size_t(0)
+    req, tile0, ntiles = ((ctypes.c_uint32 * max(cap, 1))() for _ in range(3))
+    launch = (ctypes.c_int32 * max(cap, 1))()
+    dev_tiles = (ctypes.c_uint32 * int(ndev))()
+    _check(load().p1hip_wide_ranges(arr, n, int(ndev), cap, ctypes.byref(count), req, tile0, ntiles, launch,
+                                    dev_tiles))
+    assert count.value <= cap
+    for j in range(count.value):
+        lay[req[j]]["ranges"].append((tile0[j], ntiles[j], launch[j]))
+    return lay, list(dev_tiles)
+
+
+def get_wide_stats():
+    """Accounting of scan_batch_wide since reset_stats (p1hip_get_wide_stats)."""
+    s = WideStats()
+    _check(load().p1hip_get_wide_stats(ctypes.byref(s)))
     return s.as_dict()
 
 

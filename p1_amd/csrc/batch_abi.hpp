@@ -44,9 +44,35 @@ P1_HD uint32_t batch_find_seg(const BatchSeg* segs, uint32_t nseg, uint32_t b) {
   return lo;
 }
 
+// p1hip_scan_batch_wide: the mid-size requests of a call share k_scan launches
+// (the scan code object's kernel, unchanged), whose pieces are ordered
+// longest-running first across all requests, so a request's partials are not
+// contiguous.  One range = a run of tiles of one request in the device's
+// partial array (one k_scan segment, or the request's generic tiles).
+struct WideRange {
+  uint32_t tile0, ntiles;
+};
+
+// What thread `tid` of `nthreads` folds for a request whose ranges are
+// ranges[r0 .. r1): the restatement of k_wide_reduce's loop that
+// tools/batch_emu replays (the kernel then takes the workgroup's minimum).
+P1_HD Key wide_fold_thread(const Key* part, const WideRange* ranges, uint32_t r0, uint32_t r1, uint32_t tid,
+                           uint32_t nthreads) {
+  Key m = {~0ull, ~0ull};
+  for (uint32_t j = r0; j < r1; ++j) {
+    const WideRange R = ranges[j];
+    for (uint32_t i = tid; i < R.ntiles; i += nthreads)
+      if (key_lt(part[R.tile0 + i], m)) m = part[R.tile0 + i];
+  }
+  return m;
+}
+
 // Kernel entry points (extern "C" names in the batch code object):
 //   k_batch_scan(const BatchSeg* segs, uint32_t nseg, Key* part)       grid: tiles x kBlock
 //   k_batch_reduce(const Key* part, const uint32_t* req_tile0, Key* out)
 //                                     grid: requests x kBlock; request r owns
 //                                     part[req_tile0[r] .. req_tile0[r + 1])
+//   k_wide_reduce(const Key* part, const WideRange* ranges, const uint32_t* req_range0, Key* out)
+//                                     grid: requests x kBlock; request r owns
+//                                     ranges[req_range0[r] .. req_range0[r + 1])
 }  // namespace p1

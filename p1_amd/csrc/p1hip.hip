@@ -22,8 +22,14 @@
 // (p1hip_batch_kernels.hip, p1hip_batch_blob.S); layout and tables come from
 // batch_plan.hpp, which tools/batch_emu shares.
 //
+// p1hip_scan_batch_wide: the requests of a call above the batch limit and of
+// at most 2^24 nonces share k_scan launches (the scan object's kernel, up to
+// kMaxSegs segments of any messages per launch), their generic pieces one
+// k_batch_scan launch, and k_wide_reduce (batch object) folds one result per
+// request; the layout comes from wide_plan.hpp, which tools/batch_emu shares.
+//
 // Order of this file: runtime state, helpers, the scan path, the batch path,
-// reduce_pairs, then the C ABI in one extern "C" block.  Every HIP and RCCL
+// the wide path, reduce_pairs, then the C ABI in one extern "C" block.  Every HIP and RCCL
 // call of the library is in this file (tests/test_stream_discipline.py).
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -46,6 +52,7 @@
 #include "planner.hpp"
 #include "scan_abi.hpp"
 #include "scan_pack.hpp"
+#include "wide_plan.hpp"
 
 // the embedded gfx950 code objects (p1hip_kernels_blob.S, p1hip_batch_blob.S)
 extern "C" const unsigned char p1hip_kernels_co[];
@@ -116,7 +123,7 @@ enum KnobWhen { kPerScan, kPerBatch, kAtInit };  // init: the open devices keep 
 enum KnobId {
   kSmallMaxNoncesKnob, kMaxLaunchBlocksKnob, kMaxScanSpanKnob, kKwtabMaxBytesKnob, kNoRcclKnob, kForceRcclKnob,
   kMinFastThreadsKnob, kTestFailDeviceKnob, kNoTableKnob, kNoSplitKnob, kScanGridKnob, kBatchMaxNoncesKnob,
-  kBatchMaxTilesKnob, kKnobCount
+  kBatchMaxTilesKnob, kWideMaxNoncesKnob, kWideMaxSegsKnob, kWideMinFastThreadsKnob, kKnobCount
 };
 struct Knob {
   const char* name;
@@ -157,6 +164,15 @@ const Knob kKnobs[] = {
     {"P1HIP_BATCH_MAX_TILES", kBatchMaxTiles, kBatchMaxTiles, kZeroDef, kPerBatch,
      "tiles per launch pair, so GPU tests run several launch pairs on small batches (batch_layout raises it to "
      "the largest single request's tile count)"},
+    {"P1HIP_WIDE_MAX_NONCES", kWideMaxNonces, kWideMaxNonces, kValue, kPerBatch,
+     "requests above the coalescing limit and of at most this many nonces share k_scan launches in "
+     "p1hip_scan_batch_wide; larger ones run individually (0: all of them)"},
+    {"P1HIP_WIDE_MAX_SEGS", kMaxSegs, kMaxSegs, kZeroDef, kPerBatch,
+     "segments per k_scan launch of p1hip_scan_batch_wide, so GPU tests run many launches back to back on small "
+     "calls and requests whose pieces land in different launches"},
+    {"P1HIP_WIDE_MIN_FAST_THREADS", 0, ~0ull, kZeroDef, kPerBatch,
+     "occupancy floor the wide requests are planned with instead of wide_min_fast_threads' rule (the default, "
+     "0); 1 keeps k = 3"},
 };
 static_assert(sizeof kKnobs / sizeof kKnobs[0] == kKnobCount, "one row per KnobId, in its order");
 
@@ -254,7 +270,7 @@ struct Dev {
   // p1hip_scan_batch: its own code object and buffers (grown on demand, kept
   // across calls; no p1hip_scan touches them)
   hipModule_t bmod = nullptr;
-  hipFunction_t f_bscan = nullptr, f_breduce = nullptr;
+  hipFunction_t f_bscan = nullptr, f_breduce = nullptr, f_wreduce = nullptr;
   DevBuf<BatchSeg> d_bseg;      // segment table of one launch pair
   PinnedBuf<BatchSeg> h_bseg;   // staging
   DevBuf<uint32_t> d_btile0;    // first tile of each request (+ end)
@@ -262,6 +278,10 @@ struct Dev {
   DevBuf<Key> d_bout;           // one Key per request
   PinnedBuf<Key> h_bout;
   DevBuf<Key> d_bpart;          // one partial per tile
+  // p1hip_scan_batch_wide: its range table (the rest it shares: d_part, d_seg
+  // and the ticket with p1hip_scan, d_bseg, d_btile0 and d_bout with the batch)
+  DevBuf<WideRange> d_wrange;
+  PinnedBuf<WideRange> h_wrange;
   std::vector<hipEvent_t> evs;  // profiling event pool (pairs)
   // MODE 5 K+W tables on this device, least recently used first (built by
   // k_kwtable; keyed by the block-1 template and k)
@@ -292,6 +312,7 @@ struct Runtime {
   int fail_device = -1;
   p1hip_stats_t stats{};
   p1hip_batch_stats_t bstats{};
+  p1hip_wide_stats_t wstats{};
 };
 
 // Never destroyed: the runtime state outlives every static destructor, so a
@@ -423,6 +444,7 @@ int init_devs(Runtime& R, const std::vector<int>& ords) {
     HIPCHK(hipModuleLoadData(&d.bmod, p1hip_batch_co));
     HIPCHK(hipModuleGetFunction(&d.f_bscan, d.bmod, "k_batch_scan"));
     HIPCHK(hipModuleGetFunction(&d.f_breduce, d.bmod, "k_batch_reduce"));
+    HIPCHK(hipModuleGetFunction(&d.f_wreduce, d.bmod, "k_wide_reduce"));
     // fixed-size buffers: floor = need, so exactly that many elements
     HIPCHK(d.d_small_part.reserve(kSmallMaxBlocks, kSmallMaxBlocks));
     HIPCHK(d.d_ticket.reserve(1, 1));
@@ -860,9 +882,9 @@ int batch_reserve(Dev& d, size_t nseg, size_t nreq, size_t tiles) {
   return P1HIP_OK;
 }
 
-int scan_batch_locked(const p1hip_request_t* reqs, size_t n, p1hip_result_t* out) {
-  Runtime& R = rt();
-  std::lock_guard<std::mutex> g(R.mu);
+// One p1hip_scan_batch with R.mu held by the caller (p1hip_scan_batch;
+// p1hip_scan_batch_wide for its small requests).
+int scan_batch_held(Runtime& R, const p1hip_request_t* reqs, size_t n, p1hip_result_t* out) {
   const auto t0 = std::chrono::steady_clock::now();
   int rc = ensure_init(R);
   if (rc) return rc;
@@ -941,6 +963,166 @@ int scan_batch_locked(const p1hip_request_t* reqs, size_t n, p1hip_result_t* out
   R.bstats.tiles += tiles;
   R.bstats.nonces += nonces;
   R.bstats.wall_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return P1HIP_OK;
+}
+
+int scan_batch_locked(const p1hip_request_t* reqs, size_t n, p1hip_result_t* out) {
+  Runtime& R = rt();
+  std::lock_guard<std::mutex> g(R.mu);
+  return scan_batch_held(R, reqs, n, out);
+}
+
+// ----------------------------------------------------------------------------
+// p1hip_scan_batch_wide
+// ----------------------------------------------------------------------------
+// The layout of a wide call as the knobs in force give it (R.mu held: the
+// split setting is the open devices', or the environment's before any init).
+std::string wide_layout_held(const Runtime& R, const std::vector<BatchReq>& q, int ndev, WideLayout& Y) {
+  const bool split = R.devs.empty() ? !knob(kNoSplitKnob) : R.split;
+  return wide_layout(q.data(), q.size(), ndev, knob(kBatchMaxNoncesKnob), knob(kWideMaxNoncesKnob),
+                     (uint32_t)knob(kWideMaxSegsKnob), knob(kWideMinFastThreadsKnob), split, Y);
+}
+
+// Room on device d for its part of a wide call.  Called only while the stream
+// is idle (every call ends with a synchronisation).
+int wide_reserve(Dev& d, const WideDevice& D) {
+  const size_t nreq = D.reqs.size();
+  HIPCHK(d.d_part.reserve(D.total_tiles, 1));
+  HIPCHK(d.d_seg.reserve(D.fast.size(), 4 * kMaxSegs));
+  HIPCHK(d.h_seg.reserve(D.fast.size(), 4 * kMaxSegs));
+  HIPCHK(d.d_bseg.reserve(D.gsegs.size(), 64));
+  HIPCHK(d.h_bseg.reserve(D.gsegs.size(), 64));
+  HIPCHK(d.d_wrange.reserve(D.ranges.size(), 64));
+  HIPCHK(d.h_wrange.reserve(D.ranges.size(), 64));
+  HIPCHK(d.d_btile0.reserve(nreq, 64, 1));
+  HIPCHK(d.h_btile0.reserve(nreq, 64, 1));
+  HIPCHK(d.d_bout.reserve(nreq, 64));
+  HIPCHK(d.h_bout.reserve(nreq, 64));
+  return P1HIP_OK;
+}
+
+// Enqueue device d's part of a wide call on its stream: the tables, one
+// k_batch_scan for the generic pieces, the k_scan launches back to back (the
+// ticket is zero between launches, as in a multi-launch p1hip_scan), the
+// per-request fold and the copy back.  No synchronisation.
+int wide_enqueue(Dev& d, const WideDevice& D) {
+  const size_t nreq = D.reqs.size();
+  HIPCHK(hipSetDevice(d.ordinal));
+  int rc = wide_reserve(d, D);
+  if (rc) return rc;
+  // segment tables of all k_scan launches, back to back (W.first is the launch's offset)
+  for (const WideLaunch& W : D.launches) {
+    const std::string err = wide_fill_launch(D, W, d.h_seg.p + W.first);
+    if (!err.empty()) return fail(P1HIP_ERR_ARGS, err);
+  }
+  if (!D.fast.empty())
+    HIPCHK(hipMemcpyAsync(d.d_seg.p, d.h_seg.p, D.fast.size() * sizeof(Segment), hipMemcpyHostToDevice, d.stream));
+  memcpy(d.h_wrange.p, D.ranges.data(), D.ranges.size() * sizeof(WideRange));
+  memcpy(d.h_btile0.p, D.req_range0.data(), (nreq + 1) * sizeof(uint32_t));
+  HIPCHK(hipMemcpyAsync(d.d_wrange.p, d.h_wrange.p, D.ranges.size() * sizeof(WideRange), hipMemcpyHostToDevice,
+                        d.stream));
+  HIPCHK(hipMemcpyAsync(d.d_btile0.p, d.h_btile0.p, (nreq + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, d.stream));
+  if (D.gen_tiles) {
+    memcpy(d.h_bseg.p, D.gsegs.data(), D.gsegs.size() * sizeof(BatchSeg));
+    HIPCHK(hipMemcpyAsync(d.d_bseg.p, d.h_bseg.p, D.gsegs.size() * sizeof(BatchSeg), hipMemcpyHostToDevice, d.stream));
+    HIPCHK(launch(d.f_bscan, D.gen_tiles, kBlock, d.stream, (const BatchSeg*)d.d_bseg.p, (uint32_t)D.gsegs.size(),
+                  (Key*)(d.d_part.p + D.gen_tile0)));
+  }
+  for (const WideLaunch& W : D.launches) {
+#ifdef P1_STATIC_GRID
+    HIPCHK(launch(d.f_scan, W.tiles, kBlock, d.stream, (const Segment*)(d.d_seg.p + W.first), (uint32_t)W.count,
+                  (Key*)(d.d_part.p + W.tile0)));
+#else
+    HIPCHK(launch(d.f_scan, scan_grid_for(d, W.tiles), kBlock, d.stream, (const Segment*)(d.d_seg.p + W.first),
+                  (uint32_t)W.count, (Key*)(d.d_part.p + W.tile0), (uint32_t)W.tiles, d.d_scan_ticket.p));
+#endif
+  }
+  HIPCHK(launch(d.f_wreduce, (uint32_t)nreq, kBlock, d.stream, (const Key*)d.d_part.p,
+                (const WideRange*)d.d_wrange.p, (const uint32_t*)d.d_btile0.p, d.d_bout.p));
+  HIPCHK(hipMemcpyAsync(d.h_bout.p, d.d_bout.p, nreq * sizeof(Key), hipMemcpyDeviceToHost, d.stream));
+  return P1HIP_OK;
+}
+
+int scan_batch_wide_locked(const p1hip_request_t* reqs, size_t n, p1hip_result_t* out) {
+  Runtime& R = rt();
+  std::lock_guard<std::mutex> g(R.mu);
+  const auto t0 = std::chrono::steady_clock::now();
+  int rc = ensure_init(R);
+  if (rc) return rc;
+  const std::vector<BatchReq> q = batch_reqs(reqs, n);
+  WideLayout Y;
+  const std::string lerr = wide_layout_held(R, q, (int)R.devs.size(), Y);
+  if (!lerr.empty()) return fail(P1HIP_ERR_ARGS, lerr);
+  // results are gathered here and copied to `out` only when the whole call has succeeded
+  std::vector<p1hip_result_t> res(n, p1hip_result_t{~0ull, 0});
+  // Small requests: p1hip_scan_batch's own path, as one batch.
+  if (Y.small) {
+    std::vector<p1hip_request_t> sq;
+    std::vector<size_t> idx;
+    for (size_t i = 0; i < n; ++i)
+      if (Y.route[i] == kWideRouteSmall) {
+        sq.push_back(reqs[i]);
+        idx.push_back(i);
+      }
+    std::vector<p1hip_result_t> so(sq.size());
+    if ((rc = scan_batch_held(R, sq.data(), sq.size(), so.data())) != P1HIP_OK) return rc;
+    for (size_t j = 0; j < idx.size(); ++j) res[idx[j]] = so[j];
+  }
+  // Wide requests: every device's launches are enqueued before any stream is
+  // synchronised, so the devices run side by side.
+  p1hip_wide_stats_t add{};
+  auto run = [&]() -> int {
+    for (size_t dv = 0; dv < Y.devs.size(); ++dv) {
+      const WideDevice& D = Y.devs[dv];
+      if (D.reqs.empty()) continue;
+      if ((rc = wide_enqueue(R.devs[dv], D)) != P1HIP_OK) return rc;
+      add.scan_launches += D.launches.size();
+      add.scan_segments += D.fast.size();
+      add.generic_launches += D.gen_tiles ? 1 : 0;
+      add.generic_segments += D.gsegs.size();
+      add.tiles += D.total_tiles;
+      add.nonces += D.nonces;
+    }
+    for (size_t dv = 0; dv < Y.devs.size(); ++dv) {
+      const WideDevice& D = Y.devs[dv];
+      if (D.reqs.empty()) continue;
+      Dev& d = R.devs[dv];
+      HIPCHK(hipStreamSynchronize(d.stream));
+      for (size_t r = 0; r < D.reqs.size(); ++r) {
+        const Key kq = finish_key(d.h_bout.p[r]);
+        res[D.reqs[r]] = p1hip_result_t{kq.h, kq.n};
+      }
+    }
+    // Larger requests: one by one through the multi-device scan path.
+    for (size_t i = 0; i < n; ++i)
+      if (Y.route[i] == kWideRouteIndividual) {
+        rc = scan_held(R, q[i].msg, q[i].len, q[i].lower, q[i].upper, &res[i].hash, &res[i].nonce);
+        if (rc) return fail(rc, "request " + std::to_string(i) + ": " + g_err);
+      }
+    return P1HIP_OK;
+  };
+  if ((rc = run()) != P1HIP_OK) {
+    // leave nothing in flight behind a failed call: the next call rewrites the pinned staging tables
+    const std::string keep = g_err;
+    for (Dev& d : R.devs) (void)hipStreamSynchronize(d.stream);
+    g_err = keep;
+    return rc;
+  }
+  for (size_t i = 0; i < n; ++i) out[i] = res[i];
+  p1hip_wide_stats_t& S = R.wstats;
+  S.calls++;
+  S.requests += n;
+  S.empty += Y.empty;
+  S.small += Y.small;
+  S.wide += Y.wide;
+  S.individual += Y.individual;
+  S.scan_launches += add.scan_launches;
+  S.scan_segments += add.scan_segments;
+  S.generic_launches += add.generic_launches;
+  S.generic_segments += add.generic_segments;
+  S.tiles += add.tiles;
+  S.nonces += add.nonces;
+  S.wall_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   return P1HIP_OK;
 }
 
@@ -1064,6 +1246,77 @@ int p1hip_get_batch_stats(p1hip_batch_stats_t* out) {
   return P1HIP_OK;
 }
 
+int p1hip_scan_batch_wide(const p1hip_request_t* reqs, size_t n, p1hip_result_t* out) {
+  if (n == 0) return P1HIP_OK;
+  if (!reqs || !out) return fail(P1HIP_ERR_ARGS, "null request or result array");
+  return guarded([&]() {
+    const int rc = batch_check(reqs, n);
+    return rc ? rc : scan_batch_wide_locked(reqs, n, out);
+  });
+}
+
+int p1hip_wide_layout(const p1hip_request_t* reqs, size_t n, int ndev, int32_t* route, int32_t* device,
+                      uint32_t* segs, uint32_t* tiles) {
+  if (ndev <= 0) return fail(P1HIP_ERR_ARGS, "ndev <= 0");
+  if (n == 0) return P1HIP_OK;
+  if (!reqs || !route || !device || !segs || !tiles) return fail(P1HIP_ERR_ARGS, "null request or output array");
+  return guarded([&]() {
+    const int rc = batch_check(reqs, n);
+    if (rc) return rc;
+    Runtime& R = rt();
+    std::lock_guard<std::mutex> g(R.mu);
+    WideLayout Y;
+    const std::string err = wide_layout_held(R, batch_reqs(reqs, n), ndev, Y);
+    if (!err.empty()) return fail(P1HIP_ERR_ARGS, err);
+    for (size_t i = 0; i < n; ++i) {
+      route[i] = Y.route[i];
+      device[i] = Y.device[i];
+      segs[i] = Y.segs[i];
+      tiles[i] = Y.tiles[i];
+    }
+    return P1HIP_OK;
+  });
+}
+
+int p1hip_wide_ranges(const p1hip_request_t* reqs, size_t n, int ndev, size_t cap, size_t* count, uint32_t* req,
+                      uint32_t* tile0, uint32_t* ntiles, int32_t* launch, uint32_t* dev_tiles) {
+  if (ndev <= 0) return fail(P1HIP_ERR_ARGS, "ndev <= 0");
+  if (!count || !dev_tiles || (cap && (!req || !tile0 || !ntiles || !launch)) || (n && !reqs))
+    return fail(P1HIP_ERR_ARGS, "null request or output array");
+  return guarded([&]() {
+    const int rc = batch_check(reqs, n);
+    if (rc) return rc;
+    Runtime& R = rt();
+    std::lock_guard<std::mutex> g(R.mu);
+    WideLayout Y;
+    const std::string err = wide_layout_held(R, batch_reqs(reqs, n), ndev, Y);
+    if (!err.empty()) return fail(P1HIP_ERR_ARGS, err);
+    size_t k = 0;
+    for (int dv = 0; dv < ndev; ++dv) {
+      const WideDevice& D = Y.devs[(size_t)dv];
+      dev_tiles[dv] = D.total_tiles;
+      for (size_t r = 0; r < D.reqs.size(); ++r)
+        for (uint32_t j = D.req_range0[r]; j < D.req_range0[r + 1]; ++j, ++k) {
+          if (k >= cap) continue;
+          req[k] = (uint32_t)D.reqs[r];
+          tile0[k] = D.ranges[j].tile0;
+          ntiles[k] = D.ranges[j].ntiles;
+          launch[k] = D.range_launch[j];
+        }
+    }
+    *count = k;
+    return P1HIP_OK;
+  });
+}
+
+int p1hip_get_wide_stats(p1hip_wide_stats_t* out) {
+  if (!out) return fail(P1HIP_ERR_ARGS, "null stats pointer");
+  Runtime& R = rt();
+  std::lock_guard<std::mutex> g(R.mu);
+  *out = R.wstats;
+  return P1HIP_OK;
+}
+
 int p1hip_plan_shards(const uint8_t* msg, size_t msg_len, uint64_t lower, uint64_t upper, int n,
                       uint64_t* first, uint64_t* last) {
   if (n <= 0 || !first || !last) return fail(P1HIP_ERR_ARGS, "n <= 0 or null output");
@@ -1110,6 +1363,7 @@ void p1hip_reset_stats(void) {
   std::lock_guard<std::mutex> g(R.mu);
   R.stats = p1hip_stats_t{};
   R.bstats = p1hip_batch_stats_t{};
+  R.wstats = p1hip_wide_stats_t{};
   for (Dev& d : R.devs) {
     d.acc = p1hip_device_stats_t{};
     d.acc.shard_first = 1;  // empty until the next scan

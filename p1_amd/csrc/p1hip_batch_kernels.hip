@@ -1,5 +1,6 @@
 // p1hip_batch_kernels.hip -- the second gfx950 code object of libp1hip.so:
-// the kernels of p1hip_scan_batch (many small requests in one launch pair).
+// the kernels of p1hip_scan_batch (many small requests in one launch pair)
+// and the per-request fold of p1hip_scan_batch_wide (k_wide_reduce).
 //
 // Only the generic per-thread path (scan_core.hpp generic_thread), so it
 // compiles in seconds and needs no tools/isa_post.py pass; it is built
@@ -41,5 +42,25 @@ extern "C" __global__ __launch_bounds__(kBlock) void k_batch_reduce(const Key* _
   const uint32_t t1 = req_tile0[r + 1];
   Key m = {~0ull, ~0ull};
   for (uint32_t i = req_tile0[r] + threadIdx.x; i < t1; i += kBlock) m = key_min(m, part[i]);
+  block_min_store<kBlock>(m, out + r);
+}
+
+// p1hip_scan_batch_wide: one workgroup per request folds the request's
+// ranges of the device's partial array (batch_abi.hpp WideRange: one range
+// per k_scan segment of the request, one for its generic tiles).  The range
+// table is indexed by the workgroup's request, so its loads are wave-uniform;
+// the partials were written by earlier kernels on the stream (no fence, no
+// atomics).  A range of a 2^24-nonce request has at most 6554 tiles.
+extern "C" __global__ __launch_bounds__(kBlock) void k_wide_reduce(const Key* __restrict__ part,
+                                                                   const WideRange* __restrict__ ranges,
+                                                                   const uint32_t* __restrict__ req_range0,
+                                                                   Key* __restrict__ out) {
+  const uint32_t r = blockIdx.x;
+  const uint32_t j1 = req_range0[r + 1];
+  Key m = {~0ull, ~0ull};
+  for (uint32_t j = req_range0[r]; j < j1; ++j) {
+    const uint32_t t0 = ranges[j].tile0, nt = ranges[j].ntiles;
+    for (uint32_t i = threadIdx.x; i < nt; i += kBlock) m = key_min(m, part[t0 + i]);
+  }
   block_min_store<kBlock>(m, out + r);
 }

@@ -77,6 +77,9 @@ bitcoin::Message HandleRequest(const bitcoin::Message& req, uint64_t chunk = kDe
 // order, each what HandleRequest returns for it.  Requests of more than
 // `chunk` nonces go through ScanChunked one by one; all others share one
 // p1hip_scan_batch call, which coalesces the small ones into one launch pair.
-std::vector<bitcoin::Message> HandleBatch(const std::vector<bitcoin::Message>& reqs, uint64_t chunk = kDefaultChunk);
+// `wide`: through p1hip_scan_batch_wide instead, where the requests above 2^16
+// and of at most 2^24 nonces share k_scan launches as well.
+std::vector<bitcoin::Message> HandleBatch(const std::vector<bitcoin::Message>& reqs, uint64_t chunk = kDefaultChunk,
+                                          bool wide = false);
 
 }  // namespace miner

@@ -2,7 +2,7 @@
 // libp1hip.so's C ABI: bitcoin::Hash (hash.go:13-17) and the miner's scan
 // step with miner-side chunking (miner.go:55-66).  Every hash is computed by
 // the library; there is no CPU path.  HandleBatch answers many requests
-// through one p1hip_scan_batch call.
+// through one p1hip_scan_batch (or p1hip_scan_batch_wide) call.
 #include <string>
 #include <vector>
 
@@ -54,7 +54,7 @@ bitcoin::Message HandleRequest(const bitcoin::Message& req, uint64_t chunk) {
   return bitcoin::NewResult(h, n);
 }
 
-std::vector<bitcoin::Message> HandleBatch(const std::vector<bitcoin::Message>& reqs, uint64_t chunk) {
+std::vector<bitcoin::Message> HandleBatch(const std::vector<bitcoin::Message>& reqs, uint64_t chunk, bool wide) {
   if (chunk == 0) chunk = kDefaultChunk;
   std::vector<bitcoin::Message> res(reqs.size());
   std::vector<p1hip_request_t> q;
@@ -69,8 +69,10 @@ std::vector<bitcoin::Message> HandleBatch(const std::vector<bitcoin::Message>& r
     }
   }
   std::vector<p1hip_result_t> out(q.size());
-  const int rc = p1hip_scan_batch(q.data(), q.size(), out.data());
-  if (rc != P1HIP_OK) throw bitcoin::HipError(rc, std::string("p1hip_scan_batch: ") + p1hip_last_error());
+  const int rc = wide ? p1hip_scan_batch_wide(q.data(), q.size(), out.data())
+                      : p1hip_scan_batch(q.data(), q.size(), out.data());
+  if (rc != P1HIP_OK)
+    throw bitcoin::HipError(rc, std::string(wide ? "p1hip_scan_batch_wide: " : "p1hip_scan_batch: ") + p1hip_last_error());
   for (size_t j = 0; j < idx.size(); ++j) res[idx[j]] = bitcoin::NewResult(out[j].hash, out[j].nonce);
   return res;
 }

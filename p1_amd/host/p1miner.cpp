@@ -14,7 +14,7 @@
 //   p1miner scan <msg> <lower> <upper>   prints "Result <hash> <nonce>"
 //                                        (the client's output, client.go:59-61)
 //   p1miner hash <msg> <nonce>           prints bitcoin.Hash(msg, nonce)
-//   p1miner serve [--device N] [--chunk C] [--batch B]
+//   p1miner serve [--device N] [--chunk C] [--batch B [--wide]]
 //                                        one JSON Message per stdin line; every
 //                                        line is answered with one JSON Result
 //                                        line (miner.go:49-67 scans whatever it
@@ -23,7 +23,10 @@
 //                                        collected and answered together, in
 //                                        order, through one p1hip_scan_batch
 //                                        call, on the B-th line, on an empty
-//                                        line (itself not answered) or at EOF
+//                                        line (itself not answered) or at EOF;
+//                                        --wide: through p1hip_scan_batch_wide,
+//                                        so requests of up to 2^24 nonces share
+//                                        launches too (no effect without --batch)
 //   p1miner json                         re-marshals stdin JSON lines (no GPU;
 //                                        wire-format tests): "ERROR" for a
 //                                        syntax error, "TYPEERROR\t" before
@@ -56,7 +59,7 @@
 static int usage() {
   fprintf(stderr,
           "usage: p1miner scan <msg> <lower> <upper> | hash <msg> <nonce> | "
-          "serve [--device N] [--chunk C] [--batch B] | lsp <host:port> [--device N] [--chunk C] [--epoch-limit K] "
+          "serve [--device N] [--chunk C] [--batch B [--wide]] | lsp <host:port> [--device N] [--chunk C] [--epoch-limit K] "
           "[--epoch-millis M] [--window W] [--copies K] [--connect-copies K] | json | lsp-json | lsp-wrap <connID> <seq> | lsp-unwrap\n");
   return 2;
 }
@@ -190,10 +193,12 @@ int main(int argc, char** argv) {
     if (cmd == "serve") {
       int dev = -1;
       uint64_t chunk = miner::kDefaultChunk, batch = 1;
+      bool wide = false;
       for (int i = 2; i < argc; ++i) {
         if (!strcmp(argv[i], "--device") && i + 1 < argc) dev = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--chunk") && i + 1 < argc) { if (!parse_u64(argv[++i], &chunk)) return usage(); }
         else if (!strcmp(argv[i], "--batch") && i + 1 < argc) { if (!parse_u64(argv[++i], &batch) || batch == 0) return usage(); }
+        else if (!strcmp(argv[i], "--wide")) wide = true;
         else return usage();
       }
       int rc = dev >= 0 ? p1hip_init_devices(&dev, 1) : p1hip_init(0, nullptr);
@@ -204,7 +209,7 @@ int main(int argc, char** argv) {
         // written together, one Result line per request line, in order
         std::vector<bitcoin::Message> reqs;
         auto flush = [&]() {
-          for (const bitcoin::Message& res : miner::HandleBatch(reqs, chunk)) printf("%s\n", bitcoin::Marshal(res).c_str());
+          for (const bitcoin::Message& res : miner::HandleBatch(reqs, chunk, wide)) printf("%s\n", bitcoin::Marshal(res).c_str());
           fflush(stdout);
           reqs.clear();
         };

@@ -37,6 +37,7 @@
 #include <vector>
 
 #include "../p1_amd/csrc/scan_pack.hpp"
+#include "scan_replay.hpp"
 
 using namespace p1;
 
@@ -65,32 +66,8 @@ static Key dispatch_fast(const Launch& L0) {
   exit(3);
 }
 
-// One tile of k_scan: the workgroup's kBlock threads and their minimum.  The
-// segment walk is p1emu's own copy of the two lines in p1hip_kernels.hip
-// scan_tile (the kernel source is not shared with the host).
-static Key scan_tile(const Segment* segs, uint32_t nseg, uint32_t b) {
-  uint32_t si = 0;
-  while (si + 1 < nseg && segs[si + 1].block0 <= b) ++si;
-  const Segment& S = segs[si];
-  Key m = {~0ull, ~0ull};
-  for (uint32_t t = 0; t < (uint32_t)kBlock; ++t) {
-    const uint32_t local = (b - S.block0) * kBlock + t;
-    Key k;
-    switch (S.kind) {
-#define P1_CASE(FV, NV, TR)                   \
-  case variant_id(FV, NV, TR):                \
-    k = fast_thread<FV, NV, TR>(S.fa, local); \
-    break;
-#include "../p1_amd/csrc/fast_variants.inc"
-#undef P1_CASE
-      default:
-        k = generic_thread(S.ga, local);
-        break;
-    }
-    if (key_lt(k, m)) m = k;
-  }
-  return m;
-}
+// One tile of k_scan (scan_replay.hpp, shared with tools/batch_emu).
+static Key scan_tile(const Segment* segs, uint32_t nseg, uint32_t b) { return replay_scan_tile(segs, nseg, b); }
 
 static std::vector<uint8_t> unhex(const char* s) {
   std::vector<uint8_t> v;
