@@ -95,6 +95,34 @@ int p1hip_hash(const uint8_t *msg, size_t msg_len, uint64_t nonce, uint64_t *out
 int p1hip_reduce_pairs(const uint64_t *hashes, const uint64_t *nonces, size_t n,
                        uint64_t *out_hash, uint64_t *out_nonce);
 
+/* Test hook like p1hip_reduce_pairs, for the per-tile witness of
+ * tests/test_gpu_tiles.py: one scan of [lower, upper] (1 .. 2^32 nonces; an
+ * empty or larger range is P1HIP_ERR_ARGS) on the first open device, through
+ * the very code p1hip_scan runs for a share of that size (k_scan launches +
+ * k_reduce, or k_scan_small for at most 2^16 nonces; same planner settings,
+ * tables, packing and test knobs), with two additions: the scan's slice of
+ * the partial array is filled with the byte P1HIP_TILE_POISON first (on the
+ * device's own stream), and every workgroup partial is copied back raw.
+ * tiles[i] is entry i of the partial array: the launch and tile that wrote
+ * it, its segment's kind (variant id, 255 = generic) and k, the tile's exact
+ * nonce set -- `nruns` <= 4 strided runs: run r covers, for j in [0, count),
+ * the run_len consecutive nonces from first + j * stride; nruns == 0 is a
+ * tile without a valid thread, whose partial is (UINT64_MAX, UINT64_MAX) --
+ * and the (hash, nonce) found there.  The map is that of the plan and packing
+ * actually launched.  *count receives the number of tiles; only the first
+ * `cap` entries are written.  *route: 0 = k_scan, 1 = k_scan_small.
+ * *out_hash / *out_nonce: the finished result, as p1hip_scan returns it.
+ * Counts in no statistics. */
+#define P1HIP_TILE_POISON 0xA5
+typedef struct { uint64_t first, stride; uint32_t run_len, count; } p1hip_tile_run_t;
+typedef struct {
+  uint32_t launch, tile, kind, k, nruns, reserved;
+  p1hip_tile_run_t runs[4];
+  uint64_t hash, nonce;
+} p1hip_tile_t;
+int p1hip_scan_tiles(const uint8_t *msg, size_t msg_len, uint64_t lower, uint64_t upper, size_t cap,
+                     size_t *count, p1hip_tile_t *tiles, int *route, uint64_t *out_hash, uint64_t *out_nonce);
+
 /* Many requests in one call.  A miner that serves many clients' small jobs,
  * or a chunk loop over short ranges, is bound by launch and completion
  * latency when it calls p1hip_scan once per request: a configs[0]-sized
@@ -293,7 +321,8 @@ int p1hip_comm_info(int index, int *nranks, int *rank);
  * 6 = p1hip 0.6 (p1hip_scan_batch, p1hip_batch_layout, p1hip_get_batch_stats
  * and their structs added; no existing struct changed).  Still 6 with
  * p1hip_scan_batch_wide, p1hip_wide_layout, p1hip_wide_ranges,
- * p1hip_get_wide_stats and p1hip_wide_stats_t: purely additive, the layout of
+ * p1hip_get_wide_stats and p1hip_wide_stats_t, and with the test hook
+ * p1hip_scan_tiles and its p1hip_tile_t: purely additive, the layout of
  * every existing struct is unchanged. */
 #define P1HIP_ABI_VERSION 6
 int p1hip_abi_version(void);

@@ -34,6 +34,8 @@ def load():
         lib.p1o_scan_mt.restype = ctypes.c_int
         lib.p1o_scan_mt.argtypes = [ctypes.c_char_p, ctypes.c_size_t, U64, U64, ctypes.c_int,
                                     ctypes.POINTER(U64), ctypes.POINTER(U64)]
+        lib.p1o_hashes.restype = ctypes.c_int
+        lib.p1o_hashes.argtypes = [ctypes.c_char_p, ctypes.c_size_t, U64, U64, ctypes.c_int, ctypes.c_void_p]
         lib.p1o_sha256.restype = None
         lib.p1o_sha256.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p]
         _LIB = lib
@@ -54,6 +56,19 @@ def sha256(data):
 def hash(msg, nonce):  # noqa: A001 - mirrors bitcoin.Hash
     m = _b(msg)
     return load().p1o_hash(m, len(m), int(nonce))
+
+
+def hashes(msg, first, count, threads=1):
+    """bitcoin.Hash(msg, first + i) for i in [0, count) as a numpy uint64
+    array (p1o_hashes); first + count - 1 may be 2^64 - 1, not more."""
+    import numpy as np
+
+    m = _b(msg)
+    out = np.empty(int(count), dtype=np.uint64)
+    rc = load().p1o_hashes(m, len(m), int(first), int(count), int(threads), out.ctypes.data)
+    if rc != 0:
+        raise RuntimeError("oracle hashes failed (range past 2^64 - 1?)")
+    return out
 
 
 def scan(msg, lower, upper, threads=1):

@@ -155,6 +155,7 @@ typedef struct {
     uint64_t lo, hi;
     uint64_t h, n;
     int found;
+    uint64_t *out; /* p1o_hashes: where Hash(lo) goes */
 } job_t;
 
 static void *job_run(void *p) {
@@ -194,5 +195,55 @@ int p1o_scan_mt(const uint8_t *msg, size_t len, uint64_t lower, uint64_t upper, 
     free(tid);
     *out_hash = best;
     *out_nonce = bi;
+    return rc;
+}
+
+static void *hashes_run(void *p) {
+    job_t *j = (job_t *)p;
+    uint8_t *scratch = (uint8_t *)malloc(j->len + 21);
+    if (!scratch) { j->found = -1; return NULL; }
+    uint64_t *o = j->out;
+    for (uint64_t i = j->lo;; ++i) {
+        *o++ = hash_with(j->msg, j->len, i, scratch);
+        if (i == j->hi) break; /* inclusive, no wrap at 2^64-1 */
+    }
+    free(scratch);
+    j->found = 0;
+    return NULL;
+}
+
+/* out[i] = bitcoin.Hash(msg, first + i) for i in [0, count), split contiguously
+ * over `nthreads` host threads (the per-tile checker of tests/tile_check.py
+ * takes its minima from this array).  first + count - 1 may be 2^64-1; a
+ * range that would pass it is refused (-1). */
+int p1o_hashes(const uint8_t *msg, size_t len, uint64_t first, uint64_t count, int nthreads, uint64_t *out) {
+    if (count == 0) return 0;
+    if (count - 1 > UINT64_MAX - first) return -1;
+    if (nthreads < 1) nthreads = 1;
+    if ((uint64_t)nthreads > count) nthreads = (int)count;
+    job_t *jobs = (job_t *)calloc((size_t)nthreads, sizeof(job_t));
+    pthread_t *tid = (pthread_t *)calloc((size_t)nthreads, sizeof(pthread_t));
+    if (!jobs || !tid) { free(jobs); free(tid); return -1; }
+    uint64_t per = count / (uint64_t)nthreads, extra = count % (uint64_t)nthreads;
+    uint64_t off = 0;
+    for (int t = 0; t < nthreads; ++t) {
+        uint64_t cnt = per + ((uint64_t)t < extra ? 1 : 0); /* >= 1: nthreads <= count */
+        jobs[t].msg = msg; jobs[t].len = len;
+        jobs[t].lo = first + off; jobs[t].hi = first + off + (cnt - 1);
+        jobs[t].out = out + off;
+        off += cnt;
+        if (t == nthreads - 1 || pthread_create(&tid[t], NULL, hashes_run, &jobs[t]) != 0) {
+            hashes_run(&jobs[t]); /* the last shard, or a thread that could not start, runs here */
+            tid[t] = 0;
+            jobs[t].h = 1; /* not joined */
+        }
+    }
+    int rc = 0;
+    for (int t = 0; t < nthreads; ++t) {
+        if (!jobs[t].h) pthread_join(tid[t], NULL);
+        if (jobs[t].found < 0) rc = -1;
+    }
+    free(jobs);
+    free(tid);
     return rc;
 }

@@ -22,6 +22,9 @@ from ._lib import (  # noqa: F401
     get_wide_stats,
     hash,
     reduce_pairs,
+    scan_tiles,
+    TILE_POISON,
+    TILE_GENERIC_KIND,
     plan_shards,
     set_profiling,
     get_stats,

@@ -127,6 +127,24 @@ class DeviceInfo(ctypes.Structure):
                 "arch": self.arch.decode(errors="replace"), "uuid": bytes(self.uuid).hex()}
 
 
+class TileRun(ctypes.Structure):
+    _fields_ = [("first", U64), ("stride", U64), ("run_len", ctypes.c_uint32), ("count", ctypes.c_uint32)]
+
+
+class Tile(ctypes.Structure):
+    _fields_ = [
+        ("launch", ctypes.c_uint32),
+        ("tile", ctypes.c_uint32),
+        ("kind", ctypes.c_uint32),
+        ("k", ctypes.c_uint32),
+        ("nruns", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint32),
+        ("runs", TileRun * 4),
+        ("hash", U64),
+        ("nonce", U64),
+    ]
+
+
 def lib_path():
     # P1HIP_LIB selects an alternative build of the same library (A/B tuning
     # builds under p1_amd/variants/); default is the in-tree libp1hip.so.
@@ -158,6 +176,9 @@ SIGNATURES = [
      [ctypes.c_char_p, ctypes.c_size_t, U64, U64, ctypes.c_int, ctypes.POINTER(U64), ctypes.POINTER(U64)]),
     ("p1hip_reduce_pairs", ctypes.c_int,
      [ctypes.POINTER(U64), ctypes.POINTER(U64), ctypes.c_size_t, ctypes.POINTER(U64), ctypes.POINTER(U64)]),
+    ("p1hip_scan_tiles", ctypes.c_int,
+     [ctypes.c_char_p, ctypes.c_size_t, U64, U64, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t),
+      ctypes.POINTER(Tile), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(U64), ctypes.POINTER(U64)]),
     ("p1hip_set_profiling", ctypes.c_int, [ctypes.c_int]),
     ("p1hip_get_stats", ctypes.c_int, [ctypes.POINTER(Stats)]),
     ("p1hip_reset_stats", None, []),
@@ -349,6 +370,38 @@ def reduce_pairs(hashes, nonces):
     h, o = U64(), U64()
     _check(load().p1hip_reduce_pairs(ha, na, n, ctypes.byref(h), ctypes.byref(o)))
     return h.value, o.value
+
+
+# include/p1hip.h P1HIP_TILE_POISON as a partial reads when no tile wrote it
+TILE_POISON = int.from_bytes(b"\xa5" * 8, "little")
+TILE_GENERIC_KIND = 255
+TILE_ROUTES = ("scan", "small")
+
+
+def scan_tiles(msg, lower, upper):
+    """p1hip_scan_tiles (test hook): one scan of [lower, upper] on the first
+    device with its partials poisoned first and read back raw.  Returns
+    (route ("scan" or "small"), tiles, (hash, nonce)): tiles in partial-array
+    order, each (launch, tile, kind, k, (hash, nonce), runs) with runs a list
+    of (first, run_len, stride, count) -- the layout tools/p1emu's `tiles`
+    lines parse to (tests/tile_check.py)."""
+    m = _bytes(msg)
+    lib = load()
+    count, route = ctypes.c_size_t(0), ctypes.c_int(-1)
+    h, n = U64(), U64()
+    # the tiles of a range are at most one per 256 nonces, one more per piece
+    # (ragged last tile), and the padded waves of MODE 5; ask again if short
+    cap = min(max(int(upper) - int(lower), 0) // 256 + 64, 1 << 20)
+    while True:
+        arr = (Tile * cap)()
+        _check(lib.p1hip_scan_tiles(m, len(m), int(lower), int(upper), cap, ctypes.byref(count), arr,
+                                    ctypes.byref(route), ctypes.byref(h), ctypes.byref(n)))
+        if count.value <= cap:
+            break
+        cap = count.value
+    tiles = [(t.launch, t.tile, t.kind, t.k, (t.hash, t.nonce),
+              [(r.first, r.run_len, r.stride, r.count) for r in t.runs[:t.nruns]]) for t in arr[:count.value]]
+    return TILE_ROUTES[route.value], tiles, (h.value, n.value)
 
 
 def set_profiling(on):

@@ -29,7 +29,7 @@
 // request; the layout comes from wide_plan.hpp, which tools/batch_emu shares.
 //
 // Order of this file: runtime state, helpers, the scan path, the batch path,
-// the wide path, reduce_pairs, then the C ABI in one extern "C" block.  Every HIP and RCCL
+// the wide path, reduce_pairs, scan_tiles, then the C ABI in one extern "C" block.  Every HIP and RCCL
 // call of the library is in this file (tests/test_stream_discipline.py).
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -52,6 +52,7 @@
 #include "planner.hpp"
 #include "scan_abi.hpp"
 #include "scan_pack.hpp"
+#include "tile_map.hpp"
 #include "wide_plan.hpp"
 
 // the embedded gfx950 code objects (p1hip_kernels_blob.S, p1hip_batch_blob.S)
@@ -507,9 +508,34 @@ int ensure_init(Runtime& R) {
 // ----------------------------------------------------------------------------
 // p1hip_scan
 // ----------------------------------------------------------------------------
+// The per-tile witness of p1hip_scan_tiles (test hook): run_small / run_range
+// given one fill the scan's partials with P1HIP_TILE_POISON bytes before the
+// first launch, and after the last they wait for the stream and copy the raw
+// partials and the result back, next to the tile map of the plan they ran.
+// The product path passes none: nothing is poisoned or copied there.
+struct TileDump {
+  std::vector<TileInfo> map;
+  std::vector<Key> part;
+  Key res;
+};
+
+int dump_poison(Dev& d, Key* part, size_t n) {
+  HIPCHK(hipMemsetAsync(part, P1HIP_TILE_POISON, n * sizeof(Key), d.stream));
+  return P1HIP_OK;
+}
+
+int dump_collect(Dev& d, const Key* part, TileDump& dump) {
+  dump.part.resize(dump.map.size());
+  HIPCHK(hipMemcpyAsync(dump.part.data(), part, dump.part.size() * sizeof(Key), hipMemcpyDeviceToHost, d.stream));
+  HIPCHK(hipMemcpyAsync(&dump.res, d.d_res.p, sizeof(Key), hipMemcpyDeviceToHost, d.stream));
+  HIPCHK(hipStreamSynchronize(d.stream));
+  return P1HIP_OK;
+}
+
 // Small share [lo, hi] (at most kSmallMaxNonces nonces): one k_scan_small
 // launch; the Key lands in d.d_res and, when `to_host`, in d.h_res[0].
-int run_small(Dev& d, const uint8_t* msg, size_t len, uint64_t lo, uint64_t hi, bool to_host, bool profiling) {
+int run_small(Dev& d, const uint8_t* msg, size_t len, uint64_t lo, uint64_t hi, bool to_host, bool profiling,
+              TileDump* dump = nullptr) {
   HIPCHK(hipSetDevice(d.ordinal));
   d.ctr = {};
   Plan plan;
@@ -523,11 +549,16 @@ int run_small(Dev& d, const uint8_t* msg, size_t len, uint64_t lo, uint64_t hi, 
   a.out_dev = d.d_res.p;
   a.out_host = to_host ? d.h_res.p : nullptr;
   int rc;
+  if (dump) {
+    dump->map = tile_map_small(plan);
+    if ((rc = dump_poison(d, a.part, a.nblocks))) return rc;
+  }
   size_t nev = 0;
   if (profiling && (rc = ev_record(d, nev))) return rc;
   HIPCHK(launch(d.f_small, a.nblocks, kBlock, d.stream, a));
   if (profiling && (rc = ev_record(d, nev))) return rc;
-  return ev_sum(d, nev);
+  if ((rc = ev_sum(d, nev))) return rc;
+  return dump ? dump_collect(d, a.part, *dump) : P1HIP_OK;
 }
 
 // Device copy of a MODE 5 launch's K+W table (cached, least recently used
@@ -604,7 +635,7 @@ uint32_t scan_grid_for(const Dev& d, uint32_t tiles) {
 
 // Run one device's share [lo, hi] (lo <= hi) and leave its Key in d.d_res.
 int run_range(Dev& d, const uint8_t* msg, size_t len, uint64_t lo, uint64_t hi, bool profiling,
-              uint64_t min_fast_threads, bool split, bool tabulate) {
+              uint64_t min_fast_threads, bool split, bool tabulate, TileDump* dump = nullptr) {
   HIPCHK(hipSetDevice(d.ordinal));
   d.range_id++;  // tables referenced from here on are pinned until the next call
   d.ctr = {};
@@ -637,6 +668,10 @@ int run_range(Dev& d, const uint8_t* msg, size_t len, uint64_t lo, uint64_t hi, 
   HIPCHK(d.d_seg.reserve(P.batches.size() * kMaxSegs, 4 * kMaxSegs));
   HIPCHK(d.h_seg.reserve(P.batches.size() * kMaxSegs, 4 * kMaxSegs));
   int rc;
+  if (dump) {
+    dump->map = tile_map(plan, P);
+    if ((rc = dump_poison(d, d.d_part.p, P.total_blocks))) return rc;
+  }
   size_t nev = 0;
   uint32_t part_off = 0;
   for (size_t bi = 0; bi < P.batches.size(); ++bi) {
@@ -659,7 +694,8 @@ int run_range(Dev& d, const uint8_t* msg, size_t len, uint64_t lo, uint64_t hi, 
     part_off += B.blocks;
   }
   HIPCHK(launch(d.f_reduce, 1, kReduceThreads, d.stream, (const Key*)d.d_part.p, P.total_blocks, d.d_res.p));
-  return ev_sum(d, nev);
+  if ((rc = ev_sum(d, nev))) return rc;
+  return dump ? dump_collect(d, d.d_part.p, *dump) : P1HIP_OK;
 }
 
 // A device's share, in pieces of at most kMaxScanSpan nonces: the plan of a
@@ -1163,6 +1199,47 @@ int reduce_pairs_locked(const uint64_t* hashes, const uint64_t* nonces, size_t n
   return P1HIP_OK;
 }
 
+// ----------------------------------------------------------------------------
+// p1hip_scan_tiles
+// ----------------------------------------------------------------------------
+// One share on the first device, routed as scan_held's phase 1 routes it
+// (k_scan_small up to P1HIP_SMALL_MAX_NONCES, else run_range with the
+// runtime's planner settings), with a TileDump.
+int scan_tiles_locked(const uint8_t* msg, size_t msg_len, uint64_t lower, uint64_t upper, size_t cap, size_t* count,
+                      p1hip_tile_t* tiles, int* route, uint64_t* out_hash, uint64_t* out_nonce) {
+  Runtime& R = rt();
+  std::lock_guard<std::mutex> g(R.mu);
+  int rc = ensure_init(R);
+  if (rc) return rc;
+  Dev& d = R.devs[0];
+  d.replans = 0;
+  TileDump dump;
+  const bool small = upper - lower < knob(kSmallMaxNoncesKnob);
+  rc = small ? run_small(d, msg, msg_len, lower, upper, false, R.profiling, &dump)
+             : run_range(d, msg, msg_len, lower, upper, R.profiling, R.min_fast_threads, R.split, R.tabulate, &dump);
+  if (rc) return rc;
+  *count = dump.map.size();
+  for (size_t i = 0; i < dump.map.size() && i < cap; ++i) {
+    const TileInfo& T = dump.map[i];
+    p1hip_tile_t& o = tiles[i];
+    memset(&o, 0, sizeof o);
+    o.launch = T.launch;
+    o.tile = T.tile;
+    o.kind = T.kind;
+    o.k = T.k;
+    o.nruns = T.nruns;
+    for (uint32_t r = 0; r < T.nruns; ++r)
+      o.runs[r] = {T.runs[r].first, T.runs[r].stride, T.runs[r].run_len, T.runs[r].count};
+    o.hash = dump.part[i].h;
+    o.nonce = dump.part[i].n;
+  }
+  *route = small ? 1 : 0;
+  const Key res = finish_key(dump.res);
+  *out_hash = res.h;
+  *out_nonce = res.n;
+  return P1HIP_OK;
+}
+
 }  // namespace
 
 // ----------------------------------------------------------------------------
@@ -1208,6 +1285,18 @@ int p1hip_scan(const uint8_t* msg, size_t msg_len, uint64_t lower, uint64_t uppe
   if (!msg && msg_len > 0) return fail(P1HIP_ERR_ARGS, "msg == NULL with msg_len > 0");
   if (msg_len > P1HIP_MAX_MSG_LEN) return fail(P1HIP_ERR_ARGS, "msg_len exceeds P1HIP_MAX_MSG_LEN");
   return guarded([&]() { return scan_locked(msg, msg_len, lower, upper, out_hash, out_nonce); });
+}
+
+int p1hip_scan_tiles(const uint8_t* msg, size_t msg_len, uint64_t lower, uint64_t upper, size_t cap, size_t* count,
+                     p1hip_tile_t* tiles, int* route, uint64_t* out_hash, uint64_t* out_nonce) {
+  if (!count || !route || !out_hash || !out_nonce || (!tiles && cap > 0))
+    return fail(P1HIP_ERR_ARGS, "null output pointer");
+  if (!msg && msg_len > 0) return fail(P1HIP_ERR_ARGS, "msg == NULL with msg_len > 0");
+  if (msg_len > P1HIP_MAX_MSG_LEN) return fail(P1HIP_ERR_ARGS, "msg_len exceeds P1HIP_MAX_MSG_LEN");
+  if (lower > upper) return fail(P1HIP_ERR_ARGS, "empty range");
+  if (upper - lower > 0xffffffffull) return fail(P1HIP_ERR_ARGS, "more than 2^32 nonces");
+  return guarded(
+      [&]() { return scan_tiles_locked(msg, msg_len, lower, upper, cap, count, tiles, route, out_hash, out_nonce); });
 }
 
 int p1hip_scan_batch(const p1hip_request_t* reqs, size_t n, p1hip_result_t* out) {

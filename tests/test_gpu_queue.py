@@ -6,6 +6,10 @@ without any error, so these scans are built to fail if that ever happens:
 the minimum of each range lies in a tile far past the first grid's worth,
 and ranges of very different tile counts alternate on the same stream, in
 one launch and split into many launches (P1HIP_MAX_LAUNCH_BLOCKS).
+That samples one planted tile of a 2^32-nonce grid; tests/test_gpu_tiles.py
+is the whole-grid form of the same property: every tile's partial of a scan,
+read back from a poisoned partial array, against the oracle's minimum over
+that tile's nonces.
 
 Answers: the survey's hashlib pin of configs[1] ([0, 2^32) of "bradfitz":
 (5256245051, 1626825724)) and the CPU oracle.

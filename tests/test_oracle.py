@@ -49,6 +49,26 @@ def test_scan_semantics(oracle_mod):
     assert U64_MAX - 10 <= n <= U64_MAX
 
 
+@pytest.mark.parametrize("threads", [1, 3, 8])
+def test_hashes_equals_hash(oracle_mod, threads):
+    """p1o_hashes (the per-tile checker's array of hashes) against p1o_hash,
+    nonce by nonce: across every decade edge, from 0, up to the top of u64,
+    for messages whose tails fill one and two blocks."""
+    firsts = [0] + [10 ** e - 3 for e in range(1, 20)] + [U64_MAX - 6]
+    for L in (0, 55, 56, 63, 64, 120):
+        m = bytes(65 + i % 26 for i in range(L))
+        for first in firsts:
+            got = oracle_mod.hashes(m, first, 7, threads)
+            assert got.dtype.name == "uint64" and len(got) == 7
+            assert [int(x) for x in got] == [oracle_mod.hash(m, first + i) for i in range(7)], (L, first)
+    assert int(oracle_mod.hashes("msg", U64_MAX, 1)[0]) == oracle_mod.hash("msg", U64_MAX)
+    assert len(oracle_mod.hashes("msg", 5, 0)) == 0
+    with pytest.raises(RuntimeError):
+        oracle_mod.hashes("msg", U64_MAX - 5, 7)  # would pass 2^64 - 1
+    big = oracle_mod.hashes("bradfitz", 0, 10000, threads)
+    assert (int(big.min()), int(big.argmin())) == oracle_mod.scan("bradfitz", 0, 9999) == (1419516646206828, 9898)
+
+
 @pytest.mark.parametrize("threads", [2, 3, 8])
 def test_mt_equals_serial(oracle_mod, threads):
     for lo, hi in [(0, 5000), (999, 1001), (10**9 - 300, 10**9 + 300)]:

@@ -9,7 +9,7 @@
 // produce a product result.
 //
 // usage: p1emu <msg-hex> <lower> <upper> [generic | minthreads=N] [nosplit] [notable]
-//              [packed=MAXBLOCKS[,MAXSEGS] | small]
+//              [packed=MAXBLOCKS[,MAXSEGS] | small] [tiles]
 //   minthreads=N sets the planner's occupancy floor (1 keeps k = 3 on small
 //   ranges, so every k = 3 variant is replayed); nosplit uses mode 2 for
 //   straddling lo digits (p1emu is built with -DP1_NV2_PLAIN); notable keeps
@@ -28,6 +28,12 @@
 //   small replays k_scan_small from the library's argument block (fill_small;
 //   generic pieces, at most 2^16 nonces).  Both also print
 //   "launches=<n> tiles=<n> segs=<n>" on stderr.
+//   tiles (with packed= or small) adds the per-tile witness of
+//   tests/test_tiles.py: the partial vector starts out poisoned (every byte
+//   0xA5, as p1hip_scan_tiles poisons the device's), and after the result
+//   line comes one line per entry of it, in order:
+//     tile <launch> <tile> <kind> <k> <hash> <nonce> <nruns> {<first> <run_len> <stride> <count>}
+//   the replayed partial and the tile's nonce set from p1_amd/csrc/tile_map.hpp
 #include <inttypes.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -37,6 +43,7 @@
 #include <vector>
 
 #include "../p1_amd/csrc/scan_pack.hpp"
+#include "../p1_amd/csrc/tile_map.hpp"
 #include "scan_replay.hpp"
 
 using namespace p1;
@@ -69,6 +76,19 @@ static Key dispatch_fast(const Launch& L0) {
 // One tile of k_scan (scan_replay.hpp, shared with tools/batch_emu).
 static Key scan_tile(const Segment* segs, uint32_t nseg, uint32_t b) { return replay_scan_tile(segs, nseg, b); }
 
+// what a partial holds before any tile wrote it (`tiles`): p1hip.h P1HIP_TILE_POISON
+static const Key kPoison = {0xA5A5A5A5A5A5A5A5ull, 0xA5A5A5A5A5A5A5A5ull};
+
+static void print_tiles(const std::vector<TileInfo>& map, const std::vector<Key>& part) {
+  for (size_t i = 0; i < map.size(); ++i) {
+    const TileInfo& T = map[i];
+    printf("tile %u %u %u %u %" PRIu64 " %" PRIu64 " %u", T.launch, T.tile, T.kind, T.k, part[i].h, part[i].n, T.nruns);
+    for (uint32_t r = 0; r < T.nruns; ++r)
+      printf(" %" PRIu64 " %u %" PRIu64 " %u", T.runs[r].first, T.runs[r].run_len, T.runs[r].stride, T.runs[r].count);
+    printf("\n");
+  }
+}
+
 static std::vector<uint8_t> unhex(const char* s) {
   std::vector<uint8_t> v;
   size_t n = strlen(s);
@@ -84,7 +104,7 @@ int main(int argc, char** argv) {
   if (argc < 4) {
     fprintf(stderr,
             "usage: %s <msg-hex|-> <lower> <upper> [generic|minthreads=N] [nosplit] [notable] "
-            "[packed=MAXBLOCKS[,MAXSEGS]|small]\n",
+            "[packed=MAXBLOCKS[,MAXSEGS]|small] [tiles]\n",
             argv[0]);
     return 2;
   }
@@ -93,13 +113,14 @@ int main(int argc, char** argv) {
   const uint64_t upper = strtoull(argv[3], nullptr, 10);
   bool generic_only = argc > 4 && strcmp(argv[4], "generic") == 0;
   uint64_t min_threads = kMinFastThreads;
-  bool split = true, tabulate = true, packed = false, small = false;
+  bool split = true, tabulate = true, packed = false, small = false, tiles_out = false;
   uint64_t max_blocks = kMaxLaunchBlocks;
   uint32_t max_segs = kMaxSegs;
   for (int i = 4; i < argc; ++i) {
     if (strncmp(argv[i], "minthreads=", 11) == 0) min_threads = strtoull(argv[i] + 11, nullptr, 10);
     if (strcmp(argv[i], "nosplit") == 0) split = false;
     if (strcmp(argv[i], "notable") == 0) tabulate = false;
+    if (strcmp(argv[i], "tiles") == 0) tiles_out = true;
     if (strcmp(argv[i], "small") == 0) small = generic_only = true;  // as run_small plans
     if (strncmp(argv[i], "packed=", 7) == 0) {
       packed = true;
@@ -110,7 +131,13 @@ int main(int argc, char** argv) {
       if (ms > 0 && ms < kMaxSegs) max_segs = (uint32_t)ms;
     }
   }
+  if (tiles_out && !packed && !small) {
+    fprintf(stderr, "tiles needs packed= or small\n");
+    return 2;
+  }
   Key best = {~0ull, ~0ull};
+  std::vector<TileInfo> tmap;  // `tiles`: the map and the partial vector it describes
+  std::vector<Key> tpart;
   int nf = 0, ng = 0;
   std::string vars;
   size_t launches = 0;
@@ -143,7 +170,7 @@ int main(int argc, char** argv) {
         fprintf(stderr, "small error: %s\n", err.c_str());
         return 1;
       }
-      std::vector<Key> part(a.nblocks);
+      std::vector<Key> part(a.nblocks, kPoison);
       for (uint32_t b = 0; b < a.nblocks; ++b) {
         uint32_t si = 0;
         while (si + 1 < a.nseg && a.block0[si + 1] <= b) ++si;
@@ -159,6 +186,10 @@ int main(int argc, char** argv) {
       launches = 1;
       tiles = a.nblocks;
       nsegs = a.nseg;
+      if (tiles_out) {
+        tmap = tile_map_small(plan);
+        tpart = part;
+      }
     } else if (packed) {
       // K+W tables in host memory, one per MODE 5 / 7 piece, by plan index
       std::vector<std::vector<uint32_t>> tabs(plan.launches.size());
@@ -171,18 +202,26 @@ int main(int argc, char** argv) {
       }
       const ScanPack P = pack_scan(plan, max_blocks, max_segs);
       std::vector<Segment> segs(max_segs);
-      std::vector<Key> part;  // one partial per tile, all launches (k_reduce folds them)
+      // one partial per tile, all launches (k_reduce folds them); each launch
+      // writes its own slice, from part_off (p1hip.hip run_range)
+      std::vector<Key> part(P.total_blocks, kPoison);
+      uint32_t part_off = 0;
       for (const ScanBatch& B : P.batches) {
         err = fill_segments(plan, P, B, tabptr.data(), segs.data(), ctr);
         if (!err.empty()) {
           fprintf(stderr, "segment error: %s\n", err.c_str());
           return 1;
         }
-        for (uint32_t b = 0; b < B.blocks; ++b) part.push_back(scan_tile(segs.data(), (uint32_t)B.count, b));
+        if ((uint64_t)part_off + B.blocks > part.size()) {
+          fprintf(stderr, "packing error: launch past the %zu packed tiles\n", part.size());
+          return 1;
+        }
+        for (uint32_t b = 0; b < B.blocks; ++b) part[part_off + b] = scan_tile(segs.data(), (uint32_t)B.count, b);
+        part_off += B.blocks;
         nsegs += B.count;
       }
-      if (part.size() != plan.total_blocks || P.total_blocks != plan.total_blocks) {
-        fprintf(stderr, "packing error: %zu tiles replayed, %u packed, %u planned\n", part.size(), P.total_blocks,
+      if (part_off != plan.total_blocks || P.total_blocks != plan.total_blocks) {
+        fprintf(stderr, "packing error: %u tiles replayed, %u packed, %u planned\n", part_off, P.total_blocks,
                 plan.total_blocks);
         return 1;
       }
@@ -190,6 +229,10 @@ int main(int argc, char** argv) {
         if (key_lt(p, best)) best = p;
       launches = P.batches.size();
       tiles = part.size();
+      if (tiles_out) {
+        tmap = tile_map(plan, P);
+        tpart = part;
+      }
     } else {
       for (const Launch& L : plan.launches) {
         Key k;
@@ -208,6 +251,7 @@ int main(int argc, char** argv) {
   }
   if (best.h == ~0ull) best.n = 0;  // identity of miner.go:56
   printf("%" PRIu64 " %" PRIu64 " %d %d %s\n", best.h, best.n, nf, ng, vars.empty() ? "-" : vars.c_str());
+  print_tiles(tmap, tpart);
   if (packed || small) fprintf(stderr, "launches=%zu tiles=%" PRIu64 " segs=%" PRIu64 "\n", launches, tiles, nsegs);
   return 0;
 }
