@@ -29,7 +29,7 @@ ISAPOST ?= --no-e64 --align-loops=3 --loop-offset=4 --pair-sched=0 --sched-amax=
 BUILD := build
 
 all: p1_amd/libp1hip.so oracle tools/p1emu tools/batch_emu p1_amd/p1miner p1_amd/p1server p1_amd/p1client tools/lsp_scenarios \
-     tools/lsp_fake_miner tools/queue_ctl tools/wcal tools/vbank tools/libp1clock.so
+     tools/lsp_fake_miner tools/lsp_fake_pool tools/pool_test tools/lsp_load tools/queue_ctl tools/wcal tools/vbank tools/libp1clock.so
 
 # The assembly and object stages are intermediates: once the code object
 # exists, a tree without them (the GPU box's copy leaves the 16 MB of .s out,
@@ -84,7 +84,7 @@ p1_amd/libp1hip.so: $(BUILD)/p1hip_host.o $(BLOBS)
 # miner / server / client programs
 HOSTSRC := p1_amd/host/bitcoin.cpp p1_amd/host/lsp_message.cpp p1_amd/host/lsp.cpp p1_amd/host/lspnet.cpp
 HOSTHDR := p1_amd/host/bitcoin.hpp p1_amd/host/lsp_message.hpp p1_amd/host/gojson.hpp p1_amd/host/lsp.hpp \
-           p1_amd/host/lspnet.hpp p1_amd/host/scheduler.hpp include/p1hip.h
+           p1_amd/host/lspnet.hpp p1_amd/host/scheduler.hpp p1_amd/host/miner_pool.hpp include/p1hip.h
 HOSTFLAGS := -O2 -std=c++17 -Wall -Wextra -pthread
 
 p1_amd/p1miner: p1_amd/host/p1miner.cpp p1_amd/host/miner_gpu.cpp $(HOSTSRC) $(HOSTHDR) p1_amd/libp1hip.so
@@ -105,6 +105,19 @@ tools/lsp_scenarios: tests/lsp/lsp_scenarios.cpp p1_amd/host/lsp.cpp p1_amd/host
 # test double: an LSP miner answering with the CPU oracle (tests/test_lsp_bitcoin.py)
 tools/lsp_fake_miner: tests/lsp/lsp_fake_miner.cpp p1_amd/host/bitcoin.cpp $(HOSTSRC) $(HOSTHDR) oracle
 	g++ $(HOSTFLAGS) -o $@ tests/lsp/lsp_fake_miner.cpp $(HOSTSRC) -Loracle -lp1oracle -Wl,-rpath,'$$ORIGIN/../oracle'
+
+# test double: the multi-connection miner pool (miner_pool.hpp) answering
+# with the CPU oracle (tests/test_pool_host.py)
+tools/lsp_fake_pool: tests/lsp/lsp_fake_pool.cpp $(HOSTSRC) $(HOSTHDR) oracle
+	g++ $(HOSTFLAGS) -o $@ tests/lsp/lsp_fake_pool.cpp $(HOSTSRC) -Loracle -lp1oracle -Wl,-rpath,'$$ORIGIN/../oracle'
+
+# test program: miner::Rounds against the direct scan (no LSP, no oracle)
+tools/pool_test: tests/pool_test.cpp p1_amd/host/miner_pool.hpp p1_amd/host/bitcoin.hpp p1_amd/host/lsp.hpp
+	g++ $(HOSTFLAGS) -o $@ tests/pool_test.cpp
+
+# measurement program: many LSP clients in one process (tools/pool_bench.py)
+tools/lsp_load: tools/lsp_load.cpp $(HOSTSRC) $(HOSTHDR)
+	g++ $(HOSTFLAGS) -o $@ tools/lsp_load.cpp $(HOSTSRC)
 
 # test program: hardware queues per process with and without a null-stream call
 tools/queue_ctl: tools/queue_ctl.cpp include/p1hip.h p1_amd/libp1hip.so
@@ -154,7 +167,7 @@ SANBASE := -O1 -g -std=c++17 -pthread -fno-omit-frame-pointer
 SAN_asan := -fsanitize=address,undefined -fno-sanitize-recover=undefined
 SAN_tsan := -fsanitize=thread
 SANDIR := $(BUILD)/san
-SANPROGS := lsp_scenarios sched_test p1server p1client lsp_fake_miner
+SANPROGS := lsp_scenarios sched_test p1server p1client lsp_fake_miner lsp_fake_pool pool_test
 sanitize: $(foreach s,asan tsan,$(addprefix $(SANDIR)/$(s)/,$(SANPROGS)))
 sanitize-emu: $(SANDIR)/asan/p1emu $(SANDIR)/asan/batch_emu
 
@@ -173,6 +186,12 @@ $(SANDIR)/%/p1client: p1_amd/host/p1client.cpp $(HOSTSRC) $(HOSTHDR)
 $(SANDIR)/%/lsp_fake_miner: tests/lsp/lsp_fake_miner.cpp $(HOSTSRC) $(HOSTHDR) oracle
 	mkdir -p $(@D)
 	$(SANCXX) $(SANBASE) $(SAN_$*) -o $@ tests/lsp/lsp_fake_miner.cpp $(HOSTSRC) -L$(CURDIR)/oracle -lp1oracle -Wl,-rpath,$(CURDIR)/oracle
+$(SANDIR)/%/lsp_fake_pool: tests/lsp/lsp_fake_pool.cpp $(HOSTSRC) $(HOSTHDR) oracle
+	mkdir -p $(@D)
+	$(SANCXX) $(SANBASE) $(SAN_$*) -o $@ tests/lsp/lsp_fake_pool.cpp $(HOSTSRC) -L$(CURDIR)/oracle -lp1oracle -Wl,-rpath,$(CURDIR)/oracle
+$(SANDIR)/%/pool_test: tests/pool_test.cpp p1_amd/host/miner_pool.hpp p1_amd/host/bitcoin.hpp p1_amd/host/lsp.hpp
+	mkdir -p $(@D)
+	$(SANCXX) $(SANBASE) $(SAN_$*) -o $@ tests/pool_test.cpp
 # the library's host runtime under ASan + UBSan (host side only: the kernels
 # are the shipped code object) and its GPU stress driver; in tools/san, not
 # build/, so that they travel to the GPU box with the tree
@@ -250,7 +269,7 @@ isa: $(BUILD)/p1hip_kernels.post.s
 	$(HIPCC) $(DEVFLAGS) -c -o /dev/null $(CSRC)/p1hip_kernels.hip -Rpass-analysis=kernel-resource-usage 2> $(BUILD)/resource.txt || true
 
 clean:
-	rm -f p1_amd/libp1hip.so tools/libp1clock.so tools/queue_ctl tools/p1emu tools/batch_emu p1_amd/p1miner p1_amd/p1server p1_amd/p1client tools/lsp_scenarios tools/lsp_fake_miner tools/wcal tools/vbank
+	rm -f p1_amd/libp1hip.so tools/libp1clock.so tools/queue_ctl tools/p1emu tools/batch_emu p1_amd/p1miner p1_amd/p1server p1_amd/p1client tools/lsp_scenarios tools/lsp_fake_miner tools/lsp_fake_pool tools/pool_test tools/lsp_load tools/wcal tools/vbank
 	rm -rf $(BUILD)/p1hip_kernels* $(BUILD)/p1hip_batch* $(BUILD)/p1hip_host.o
 	$(MAKE) -C oracle clean
 .PHONY: all oracle clean isa variant sanitize sanitize-emu sanitize-lib sanitize-lib-tsan fuzz

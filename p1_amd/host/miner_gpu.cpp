@@ -2,12 +2,14 @@
 // libp1hip.so's C ABI: bitcoin::Hash (hash.go:13-17) and the miner's scan
 // step with miner-side chunking (miner.go:55-66).  Every hash is computed by
 // the library; there is no CPU path.  HandleBatch answers many requests
-// through one p1hip_scan_batch (or p1hip_scan_batch_wide) call.
+// through one p1hip_scan_batch (or p1hip_scan_batch_wide) call; AnswerPieces
+// is the backend of the multi-connection miner's rounds (miner_pool.hpp).
 #include <string>
 #include <vector>
 
 #include "../../include/p1hip.h"
 #include "bitcoin.hpp"
+#include "miner_pool.hpp"
 
 namespace bitcoin {
 
@@ -75,6 +77,31 @@ std::vector<bitcoin::Message> HandleBatch(const std::vector<bitcoin::Message>& r
     throw bitcoin::HipError(rc, std::string(wide ? "p1hip_scan_batch_wide: " : "p1hip_scan_batch: ") + p1hip_last_error());
   for (size_t j = 0; j < idx.size(); ++j) res[idx[j]] = bitcoin::NewResult(out[j].hash, out[j].nonce);
   return res;
+}
+
+void AnswerPieces(const std::vector<Piece>& pieces, bool wide, std::vector<PieceResult>* out) {
+  out->assign(pieces.size(), PieceResult());
+  if (pieces.empty()) return;
+  if (pieces.size() == 1) {  // a light-load round costs what the single-connection miner's scan costs
+    const Piece& p = pieces[0];
+    const int rc = p1hip_scan(reinterpret_cast<const uint8_t*>(p.msg.data()), p.msg.size(), p.lower, p.upper,
+                              &(*out)[0].hash, &(*out)[0].nonce);
+    if (rc != P1HIP_OK) throw bitcoin::HipError(rc, std::string("p1hip_scan: ") + p1hip_last_error());
+    return;
+  }
+  std::vector<p1hip_request_t> q;
+  q.reserve(pieces.size());
+  for (const Piece& p : pieces)
+    q.push_back({reinterpret_cast<const uint8_t*>(p.msg.data()), p.msg.size(), p.lower, p.upper});
+  std::vector<p1hip_result_t> res(q.size());
+  const int rc = wide ? p1hip_scan_batch_wide(q.data(), q.size(), res.data())
+                      : p1hip_scan_batch(q.data(), q.size(), res.data());
+  if (rc != P1HIP_OK)
+    throw bitcoin::HipError(rc, std::string(wide ? "p1hip_scan_batch_wide: " : "p1hip_scan_batch: ") + p1hip_last_error());
+  for (size_t i = 0; i < res.size(); ++i) {
+    (*out)[i].hash = res[i].hash;
+    (*out)[i].nonce = res[i].nonce;
+  }
 }
 
 }  // namespace miner

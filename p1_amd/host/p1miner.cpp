@@ -10,6 +10,22 @@
 //                                        this thread while the LSP event loop
 //                                        keeps heartbeating, so a long GPU job
 //                                        never trips the epoch limit.
+//   p1miner lsp <host:port> --conns C [--wide] [--linger-us U] [--round-log FILE]
+//           [--stats] [the flags above]  one process, C connections (1..256),
+//                                        each a miner to the server; their jobs
+//                                        are answered in rounds, one piece of at
+//                                        most --chunk nonces of every connection's
+//                                        job per GPU call (miner_pool.hpp): one
+//                                        piece through p1hip_scan, more through
+//                                        p1hip_scan_batch, or, with --wide,
+//                                        p1hip_scan_batch_wide.  --linger-us U:
+//                                        wait up to U us for more jobs before a
+//                                        round (default 0).  --round-log FILE:
+//                                        one line per round, its index and then
+//                                        conn:lower:upper per piece.  --stats:
+//                                        one JSON line on stdout at exit.  Ends
+//                                        when every connection is lost, or on
+//                                        SIGTERM / SIGINT.
 //
 //   p1miner scan <msg> <lower> <upper>   prints "Result <hash> <nonce>"
 //                                        (the client's output, client.go:59-61)
@@ -55,12 +71,14 @@
 #include "lsp.hpp"
 #include "lsp_message.hpp"
 #include "lspnet.hpp"
+#include "miner_pool.hpp"
 
 static int usage() {
   fprintf(stderr,
           "usage: p1miner scan <msg> <lower> <upper> | hash <msg> <nonce> | "
           "serve [--device N] [--chunk C] [--batch B [--wide]] | lsp <host:port> [--device N] [--chunk C] [--epoch-limit K] "
-          "[--epoch-millis M] [--window W] [--copies K] [--connect-copies K] | json | lsp-json | lsp-wrap <connID> <seq> | lsp-unwrap\n");
+          "[--epoch-millis M] [--window W] [--copies K] [--connect-copies K] "
+          "[--conns C [--wide] [--linger-us U] [--round-log FILE] [--stats]] | json | lsp-json | lsp-wrap <connID> <seq> | lsp-unwrap\n");
   return 2;
 }
 
@@ -74,15 +92,59 @@ static bool parse_u64(const char* s, uint64_t* v) {
   return true;
 }
 
+// p1miner lsp --conns C: the GPU is open; run the pool (miner_pool.hpp) over
+// miner::AnswerPieces, print the statistics, release the GPU.
+static int run_pool(const std::string& hostport, const lsp::Params& prm, int conns, uint64_t chunk, long linger_us,
+                    bool wide, const std::string& round_log, bool want_stats) {
+  miner::PoolStats st;
+  std::string err;
+  const int rc = miner::RunPool(
+      hostport, prm, conns, chunk, linger_us,
+      [wide](const std::vector<miner::Piece>& pieces, std::vector<miner::PieceResult>* out) {
+        miner::AnswerPieces(pieces, wide, out);
+      },
+      round_log, &st, &err);
+  if (rc != 0) {
+    printf("Failed to join with server: %s\n", err.c_str());
+    return 1;
+  }
+  if (want_stats) {
+    p1hip_batch_stats_t b = {};
+    p1hip_wide_stats_t w = {};
+    p1hip_get_batch_stats(&b);
+    p1hip_get_wide_stats(&w);
+    printf("{%s, \"batch\": {\"calls\": %" PRIu64 ", \"requests\": %" PRIu64 ", \"coalesced\": %" PRIu64
+           ", \"individual\": %" PRIu64 ", \"empty\": %" PRIu64 ", \"launches\": %" PRIu64 ", \"tiles\": %" PRIu64
+           ", \"nonces\": %" PRIu64 ", \"wall_ms\": %.3f}, \"wide\": {\"calls\": %" PRIu64 ", \"requests\": %" PRIu64
+           ", \"empty\": %" PRIu64 ", \"small\": %" PRIu64 ", \"wide\": %" PRIu64 ", \"individual\": %" PRIu64
+           ", \"scan_launches\": %" PRIu64 ", \"scan_segments\": %" PRIu64 ", \"generic_launches\": %" PRIu64
+           ", \"generic_segments\": %" PRIu64 ", \"tiles\": %" PRIu64 ", \"nonces\": %" PRIu64 ", \"wall_ms\": %.3f}}\n",
+           miner::StatsJsonFields(st).c_str(), b.calls, b.requests, b.coalesced, b.individual, b.empty, b.launches, b.tiles,
+           b.nonces, b.wall_ms, w.calls, w.requests, w.empty, w.small, w.wide, w.individual, w.scan_launches,
+           w.scan_segments, w.generic_launches, w.generic_segments, w.tiles, w.nonces, w.wall_ms);
+    fflush(stdout);
+  }
+  p1hip_shutdown();
+  return 0;
+}
+
 // miner.go:13-31 (joinWithServer) + miner.go:33-73 (main loop)
 static int run_lsp(int argc, char** argv) {
   const std::string hostport = argv[2];
   int dev = -1;
   uint64_t chunk = miner::kDefaultChunk;
+  uint64_t conns = 0, linger_us = 0;
+  bool wide = false, want_stats = false;
+  std::string round_log;
   lsp::Params prm = lsp::NewParams();
   prm.Copies = lsp::DefaultAppCopies;
   for (int i = 3; i < argc; ++i) {
     if (!strcmp(argv[i], "--device") && i + 1 < argc) dev = atoi(argv[++i]);
+    else if (!strcmp(argv[i], "--conns") && i + 1 < argc) { if (!parse_u64(argv[++i], &conns) || conns < 1 || conns > 256) return usage(); }
+    else if (!strcmp(argv[i], "--linger-us") && i + 1 < argc) { if (!parse_u64(argv[++i], &linger_us) || linger_us > 60000000) return usage(); }
+    else if (!strcmp(argv[i], "--round-log") && i + 1 < argc) round_log = argv[++i];
+    else if (!strcmp(argv[i], "--wide")) wide = true;
+    else if (!strcmp(argv[i], "--stats")) want_stats = true;
     else if (!strcmp(argv[i], "--chunk") && i + 1 < argc) { if (!parse_u64(argv[++i], &chunk)) return usage(); }
     else if (!strcmp(argv[i], "--epoch-limit") && i + 1 < argc) prm.EpochLimit = atoi(argv[++i]);
     else if (!strcmp(argv[i], "--epoch-millis") && i + 1 < argc) prm.EpochMillis = atoi(argv[++i]);
@@ -91,10 +153,13 @@ static int run_lsp(int argc, char** argv) {
     else if (!strcmp(argv[i], "--connect-copies") && i + 1 < argc) prm.ConnectCopies = atoi(argv[++i]);
     else return usage();
   }
+  // the pool's flags mean nothing to the single-connection loop
+  if (conns == 0 && (wide || want_stats || linger_us || !round_log.empty())) return usage();
   // open the GPU before joining, so the first request does not pay for it
   int rc = dev >= 0 ? p1hip_init_devices(&dev, 1) : p1hip_init(0, nullptr);
   if (rc != P1HIP_OK) { fprintf(stderr, "p1hip init: %s\n", p1hip_last_error()); return 1; }
   std::string err;
+  if (conns) return run_pool(hostport, prm, (int)conns, chunk, (long)linger_us, wide, round_log, want_stats);
   std::unique_ptr<lsp::Client> cli = lsp::NewClient(hostport, prm, &err);
   if (!cli) {
     printf("Failed to join with server: %s\n", err.c_str());
