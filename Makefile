@@ -5,7 +5,7 @@ HIPFLAGS ?= -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -Wall
 LLVM ?= /opt/rocm/lib/llvm/bin
 CSRC := p1_amd/csrc
 HDRS := $(CSRC)/sha256_dev.hpp $(CSRC)/scan_core.hpp $(CSRC)/planner.hpp $(CSRC)/fast_variants.inc $(CSRC)/variant_cost.inc \
-        $(CSRC)/scan_abi.hpp $(CSRC)/scan_pack.hpp $(CSRC)/tile_map.hpp $(CSRC)/argmin_dev.hpp $(CSRC)/batch_abi.hpp $(CSRC)/batch_plan.hpp $(CSRC)/wide_plan.hpp include/p1hip.h
+        $(CSRC)/scan_abi.hpp $(CSRC)/scan_pack.hpp $(CSRC)/tile_map.hpp $(CSRC)/argmin_dev.hpp $(CSRC)/batch_abi.hpp $(CSRC)/batch_plan.hpp $(CSRC)/wide_plan.hpp $(CSRC)/async_slots.hpp include/p1hip.h
 # what the device code includes (the host-side planner does not rebuild it)
 DEVHDRS := $(CSRC)/sha256_dev.hpp $(CSRC)/scan_core.hpp $(CSRC)/fast_variants.inc $(CSRC)/scan_abi.hpp $(CSRC)/argmin_dev.hpp
 # device code: HIP C++ -> gfx950 assembly -> tools/isa_post.py post-pass
@@ -29,7 +29,8 @@ ISAPOST ?= --no-e64 --align-loops=3 --loop-offset=4 --pair-sched=0 --sched-amax=
 BUILD := build
 
 all: p1_amd/libp1hip.so oracle tools/p1emu tools/batch_emu p1_amd/p1miner p1_amd/p1server p1_amd/p1client tools/lsp_scenarios \
-     tools/lsp_fake_miner tools/lsp_fake_pool tools/pool_test tools/lsp_load tools/queue_ctl tools/wcal tools/vbank tools/libp1clock.so
+     tools/lsp_fake_miner tools/lsp_fake_pool tools/pool_test tools/async_slots_test tools/pool_pipeline_test \
+     tools/lsp_fake_pool_async tools/lsp_load tools/queue_ctl tools/wcal tools/vbank tools/libp1clock.so
 
 # The assembly and object stages are intermediates: once the code object
 # exists, a tree without them (the GPU box's copy leaves the 16 MB of .s out,
@@ -115,6 +116,19 @@ tools/lsp_fake_pool: tests/lsp/lsp_fake_pool.cpp $(HOSTSRC) $(HOSTHDR) oracle
 tools/pool_test: tests/pool_test.cpp p1_amd/host/miner_pool.hpp p1_amd/host/bitcoin.hpp p1_amd/host/lsp.hpp
 	g++ $(HOSTFLAGS) -o $@ tests/pool_test.cpp
 
+# test program: the ticket bookkeeping of p1hip_batch_submit / _wait against a model
+tools/async_slots_test: tests/async_slots_test.cpp $(CSRC)/async_slots.hpp
+	g++ $(HOSTFLAGS) -o $@ tests/async_slots_test.cpp
+
+# test program: miner::Pipeline over miner::Rounds with a hand-gated backend
+tools/pool_pipeline_test: tests/pool_pipeline_test.cpp p1_amd/host/miner_pool.hpp p1_amd/host/bitcoin.hpp p1_amd/host/lsp.hpp oracle
+	g++ $(HOSTFLAGS) -o $@ tests/pool_pipeline_test.cpp -Loracle -lp1oracle -Wl,-rpath,'$$ORIGIN/../oracle'
+
+# test double: the pool with --inflight (Submit on a worker thread) over the
+# CPU oracle (tests/test_pool_pipeline_host.py)
+tools/lsp_fake_pool_async: tests/lsp/lsp_fake_pool_async.cpp $(HOSTSRC) $(HOSTHDR) oracle
+	g++ $(HOSTFLAGS) -o $@ tests/lsp/lsp_fake_pool_async.cpp $(HOSTSRC) -Loracle -lp1oracle -Wl,-rpath,'$$ORIGIN/../oracle'
+
 # measurement program: many LSP clients in one process (tools/pool_bench.py)
 tools/lsp_load: tools/lsp_load.cpp $(HOSTSRC) $(HOSTHDR)
 	g++ $(HOSTFLAGS) -o $@ tools/lsp_load.cpp $(HOSTSRC)
@@ -167,7 +181,8 @@ SANBASE := -O1 -g -std=c++17 -pthread -fno-omit-frame-pointer
 SAN_asan := -fsanitize=address,undefined -fno-sanitize-recover=undefined
 SAN_tsan := -fsanitize=thread
 SANDIR := $(BUILD)/san
-SANPROGS := lsp_scenarios sched_test p1server p1client lsp_fake_miner lsp_fake_pool pool_test
+SANPROGS := lsp_scenarios sched_test p1server p1client lsp_fake_miner lsp_fake_pool pool_test \
+            async_slots_test pool_pipeline_test lsp_fake_pool_async
 sanitize: $(foreach s,asan tsan,$(addprefix $(SANDIR)/$(s)/,$(SANPROGS)))
 sanitize-emu: $(SANDIR)/asan/p1emu $(SANDIR)/asan/batch_emu
 
@@ -192,6 +207,15 @@ $(SANDIR)/%/lsp_fake_pool: tests/lsp/lsp_fake_pool.cpp $(HOSTSRC) $(HOSTHDR) ora
 $(SANDIR)/%/pool_test: tests/pool_test.cpp p1_amd/host/miner_pool.hpp p1_amd/host/bitcoin.hpp p1_amd/host/lsp.hpp
 	mkdir -p $(@D)
 	$(SANCXX) $(SANBASE) $(SAN_$*) -o $@ tests/pool_test.cpp
+$(SANDIR)/%/async_slots_test: tests/async_slots_test.cpp $(CSRC)/async_slots.hpp
+	mkdir -p $(@D)
+	$(SANCXX) $(SANBASE) $(SAN_$*) -o $@ tests/async_slots_test.cpp
+$(SANDIR)/%/pool_pipeline_test: tests/pool_pipeline_test.cpp p1_amd/host/miner_pool.hpp p1_amd/host/bitcoin.hpp p1_amd/host/lsp.hpp oracle
+	mkdir -p $(@D)
+	$(SANCXX) $(SANBASE) $(SAN_$*) -o $@ tests/pool_pipeline_test.cpp -L$(CURDIR)/oracle -lp1oracle -Wl,-rpath,$(CURDIR)/oracle
+$(SANDIR)/%/lsp_fake_pool_async: tests/lsp/lsp_fake_pool_async.cpp $(HOSTSRC) $(HOSTHDR) oracle
+	mkdir -p $(@D)
+	$(SANCXX) $(SANBASE) $(SAN_$*) -o $@ tests/lsp/lsp_fake_pool_async.cpp $(HOSTSRC) -L$(CURDIR)/oracle -lp1oracle -Wl,-rpath,$(CURDIR)/oracle
 # the library's host runtime under ASan + UBSan (host side only: the kernels
 # are the shipped code object) and its GPU stress driver; in tools/san, not
 # build/, so that they travel to the GPU box with the tree
@@ -269,7 +293,8 @@ isa: $(BUILD)/p1hip_kernels.post.s
 	$(HIPCC) $(DEVFLAGS) -c -o /dev/null $(CSRC)/p1hip_kernels.hip -Rpass-analysis=kernel-resource-usage 2> $(BUILD)/resource.txt || true
 
 clean:
-	rm -f p1_amd/libp1hip.so tools/libp1clock.so tools/queue_ctl tools/p1emu tools/batch_emu p1_amd/p1miner p1_amd/p1server p1_amd/p1client tools/lsp_scenarios tools/lsp_fake_miner tools/lsp_fake_pool tools/pool_test tools/lsp_load tools/wcal tools/vbank
+	rm -f p1_amd/libp1hip.so tools/libp1clock.so tools/queue_ctl tools/p1emu tools/batch_emu p1_amd/p1miner p1_amd/p1server p1_amd/p1client tools/lsp_scenarios tools/lsp_fake_miner tools/lsp_fake_pool tools/pool_test tools/lsp_load tools/wcal tools/vbank \
+	    tools/async_slots_test tools/pool_pipeline_test tools/lsp_fake_pool_async
 	rm -rf $(BUILD)/p1hip_kernels* $(BUILD)/p1hip_batch* $(BUILD)/p1hip_host.o
 	$(MAKE) -C oracle clean
 .PHONY: all oracle clean isa variant sanitize sanitize-emu sanitize-lib sanitize-lib-tsan fuzz

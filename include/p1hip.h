@@ -19,7 +19,8 @@
  * Plain C: no HIP/torch types, caller-owned buffers, no allocation crosses
  * the boundary.  `msg` is only borrowed for the duration of a call (cgo's
  * pointer-passing rule).  All calls are synchronous and serialised
- * internally; every call may be made from any host thread.
+ * internally, except the p1hip_batch_submit / p1hip_batch_wait pair below;
+ * every call may be made from any host thread.
  *
  * Return codes: 0 ok; negative values are errors (details in
  * p1hip_last_error(), a per-thread string).
@@ -234,6 +235,69 @@ typedef struct {
 } p1hip_wide_stats_t;
 int p1hip_get_wide_stats(p1hip_wide_stats_t *out);     /* cleared by p1hip_reset_stats */
 
+/* Asynchronous batches.  The calls above return when the device is done, so a
+ * caller that marshals the next call, or writes the last one's results, does
+ * so while the device idles.  p1hip_batch_submit lays a call out, copies what
+ * it needs, enqueues it and returns WITHOUT synchronising; p1hip_batch_wait
+ * blocks until that call is done and hands the results over.  Up to
+ * P1HIP_MAX_INFLIGHT tickets may be outstanding, so the device runs call k
+ * while the host prepares call k + 1 (one goroutine submits,
+ * another waits).
+ *
+ * p1hip_batch_submit(reqs, n, wide, &ticket): the call p1hip_scan_batch
+ * (wide == 0) or p1hip_scan_batch_wide (wide != 0) would make of the same
+ * requests -- the same routes, layout, tables and launches
+ * (p1hip_batch_layout / p1hip_wide_layout describe them), on each device's own
+ * stream, followed by one event per device.  Every request is validated first
+ * as the synchronous calls do (P1HIP_ERR_ARGS names the index).  `reqs` and
+ * every `msg` are borrowed only until submit returns.  n == 0 gives a ticket
+ * without opening a device (its wait returns 0); otherwise lazy init as in
+ * p1hip_scan.  With P1HIP_MAX_INFLIGHT tickets outstanding the call returns
+ * P1HIP_ERR_BUSY and enqueues nothing.  If anything fails after the first
+ * enqueue the streams are drained, no ticket is issued and the error is
+ * returned here.  *ticket is written only on success and is never 0.
+ *
+ * Requests on the individual route (more than 2^16 nonces with wide == 0,
+ * more than 2^24 with wide != 0) are NOT enqueued by submit: they need the
+ * MODE 5 tables and, with several devices, the all-gather of the p1hip_scan
+ * path, which is synchronous.  p1hip_batch_wait runs them one by one through
+ * that path once the ticket's coalesced part is done; a caller that wants
+ * overlap keeps its requests at or below the limit (the pool's --chunk).
+ *
+ * p1hip_batch_wait(ticket, out): blocks on the ticket's events -- not holding
+ * the library's lock, so other threads submit, wait and scan meanwhile --
+ * then out[i] is exactly what p1hip_scan(reqs[i]...) returns, for every i.
+ * `out` is written only on success; the ticket is spent and its slot free
+ * again on success and on error alike.  Tickets may be waited in any order
+ * and from any thread.  A ticket that is unknown, already waited (or being
+ * waited by another thread), or cancelled gives P1HIP_ERR_ARGS.
+ * p1hip_shutdown and a re-initialising p1hip_init* drain the streams and
+ * cancel every outstanding ticket.
+ *
+ * Each of the P1HIP_MAX_INFLIGHT slots owns every buffer its call writes
+ * (staging tables, device tables, partials, results), so a later submit never
+ * rewrites what an earlier ticket still reads; the synchronous calls keep
+ * their own buffers and stay legal while tickets are outstanding: they queue
+ * behind them on the stream.  A ticket's requests count in
+ * p1hip_batch_stats_t / p1hip_wide_stats_t as the synchronous call's would,
+ * when its wait succeeds (wall_ms: the time inside submit plus inside wait). */
+#define P1HIP_ERR_BUSY (-5)          /* P1HIP_MAX_INFLIGHT tickets are outstanding */
+#define P1HIP_MAX_INFLIGHT 4
+typedef uint64_t p1hip_ticket_t;     /* never 0 for a live ticket */
+int p1hip_batch_submit(const p1hip_request_t *reqs, size_t n, int wide, p1hip_ticket_t *ticket);
+int p1hip_batch_wait(p1hip_ticket_t ticket, p1hip_result_t *out);
+
+/* Accounting of the two calls above since p1hip_reset_stats. */
+typedef struct {
+  uint64_t submits;          /* p1hip_batch_submit calls that issued a ticket     */
+  uint64_t waits;            /* p1hip_batch_wait calls that succeeded             */
+  uint64_t busy;             /* submits refused with P1HIP_ERR_BUSY               */
+  uint64_t max_inflight;     /* most tickets outstanding at once                  */
+  double submit_ms;          /* host wall time inside successful submits          */
+  double wait_ms;            /* ... inside successful waits (blocking included)   */
+} p1hip_async_stats_t;
+int p1hip_get_async_stats(p1hip_async_stats_t *out);   /* cleared by p1hip_reset_stats */
+
 /* Kernel-level accounting.  One p1hip_scan = one (rarely several) launch of
  * the scan kernel k_scan per device, covering every decade of the range; a
  * share of at most 2^16 nonces is one launch of k_scan_small instead (plan in
@@ -322,8 +386,10 @@ int p1hip_comm_info(int index, int *nranks, int *rank);
  * and their structs added; no existing struct changed).  Still 6 with
  * p1hip_scan_batch_wide, p1hip_wide_layout, p1hip_wide_ranges,
  * p1hip_get_wide_stats and p1hip_wide_stats_t, and with the test hook
- * p1hip_scan_tiles and its p1hip_tile_t: purely additive, the layout of
- * every existing struct is unchanged. */
+ * p1hip_scan_tiles and its p1hip_tile_t, and with p1hip_batch_submit,
+ * p1hip_batch_wait, p1hip_get_async_stats, p1hip_async_stats_t and
+ * P1HIP_ERR_BUSY: purely additive, the layout of every existing struct is
+ * unchanged. */
 #define P1HIP_ABI_VERSION 6
 int p1hip_abi_version(void);
 

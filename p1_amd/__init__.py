@@ -20,6 +20,11 @@ from ._lib import (  # noqa: F401
     scan_batch_wide,
     wide_layout,
     get_wide_stats,
+    batch_submit,
+    batch_wait,
+    get_async_stats,
+    ERR_BUSY,
+    MAX_INFLIGHT,
     hash,
     reduce_pairs,
     scan_tiles,

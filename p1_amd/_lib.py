@@ -109,6 +109,20 @@ class WideStats(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class AsyncStats(ctypes.Structure):
+    _fields_ = [
+        ("submits", U64),
+        ("waits", U64),
+        ("busy", U64),
+        ("max_inflight", U64),
+        ("submit_ms", ctypes.c_double),
+        ("wait_ms", ctypes.c_double),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class DeviceInfo(ctypes.Structure):
     _fields_ = [
         ("ordinal", ctypes.c_int32),
@@ -171,6 +185,10 @@ SIGNATURES = [
       ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32),
       ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_uint32)]),
     ("p1hip_get_wide_stats", ctypes.c_int, [ctypes.POINTER(WideStats)]),
+    ("p1hip_batch_submit", ctypes.c_int,
+     [ctypes.POINTER(Request), ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(U64)]),
+    ("p1hip_batch_wait", ctypes.c_int, [U64, ctypes.POINTER(Result)]),
+    ("p1hip_get_async_stats", ctypes.c_int, [ctypes.POINTER(AsyncStats)]),
     ("p1hip_hash", ctypes.c_int, [ctypes.c_char_p, ctypes.c_size_t, U64, ctypes.POINTER(U64)]),
     ("p1hip_plan_shards", ctypes.c_int,
      [ctypes.c_char_p, ctypes.c_size_t, U64, U64, ctypes.c_int, ctypes.POINTER(U64), ctypes.POINTER(U64)]),
@@ -329,6 +347,41 @@ def get_wide_stats():
     """Accounting of scan_batch_wide since reset_stats (p1hip_get_wide_stats)."""
     s = WideStats()
     _check(load().p1hip_get_wide_stats(ctypes.byref(s)))
+    return s.as_dict()
+
+
+# include/p1hip.h P1HIP_ERR_BUSY, P1HIP_MAX_INFLIGHT
+ERR_BUSY = -5
+MAX_INFLIGHT = 4
+_TICKET_SIZES = {}  # ticket -> number of requests (batch_wait sizes its result array by it)
+
+
+def batch_submit(requests, wide=False):
+    """p1hip_batch_submit: enqueue the call scan_batch (or, with `wide`,
+    scan_batch_wide) would make of `requests` and return its ticket at once,
+    without waiting for the device.  At most MAX_INFLIGHT tickets may be
+    outstanding: one more raises P1HipError with rc == ERR_BUSY."""
+    arr, rows = _requests(requests)
+    t = U64(0)
+    _check(load().p1hip_batch_submit(arr, len(rows), 1 if wide else 0, ctypes.byref(t)))
+    _TICKET_SIZES[t.value] = len(rows)
+    return t.value
+
+
+def batch_wait(ticket):
+    """p1hip_batch_wait: block until `ticket`'s call is done; [(hash, nonce)]
+    in request order, each exactly what scan(msg, lower, upper) returns.  The
+    ticket is spent afterwards, on success and on error alike."""
+    n = _TICKET_SIZES.pop(int(ticket), 0)
+    out = (Result * max(n, 1))()
+    _check(load().p1hip_batch_wait(int(ticket), out))
+    return [(out[i].hash, out[i].nonce) for i in range(n)]
+
+
+def get_async_stats():
+    """Accounting of batch_submit / batch_wait since reset_stats."""
+    s = AsyncStats()
+    _check(load().p1hip_get_async_stats(ctypes.byref(s)))
     return s.as_dict()
 
 

@@ -11,6 +11,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ARTEFACTS = ["p1_amd/libp1hip.so", "oracle/libp1oracle.so", "p1_amd/p1miner", "p1_amd/p1server", "p1_amd/p1client",
              "tools/p1emu", "tools/batch_emu",
              "tools/lsp_scenarios", "tools/lsp_fake_miner", "tools/lsp_fake_pool", "tools/pool_test",
+             "tools/async_slots_test", "tools/pool_pipeline_test", "tools/lsp_fake_pool_async",
              "tools/libp1clock.so"]
 
 

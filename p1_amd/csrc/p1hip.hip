@@ -28,8 +28,14 @@
 // k_batch_scan launch, and k_wide_reduce (batch object) folds one result per
 // request; the layout comes from wide_plan.hpp, which tools/batch_emu shares.
 //
+// p1hip_batch_submit / p1hip_batch_wait: the same two calls without the
+// synchronisation.  submit enqueues the call in the buffers of one of
+// P1HIP_MAX_INFLIGHT slots (SlotDev; tickets: async_slots.hpp) and records an
+// event per device; wait blocks on the events with the runtime mutex released.
+// Still one stream per device: k_scan's work-queue ticket is shared.
+//
 // Order of this file: runtime state, helpers, the scan path, the batch path,
-// the wide path, reduce_pairs, scan_tiles, then the C ABI in one extern "C" block.  Every HIP and RCCL
+// the wide path, submit / wait, reduce_pairs, scan_tiles, then the C ABI in one extern "C" block.  Every HIP and RCCL
 // call of the library is in this file (tests/test_stream_discipline.py).
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -40,6 +46,7 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <condition_variable>
 #include <exception>
 #include <mutex>
 #include <string>
@@ -48,6 +55,7 @@
 #include <vector>
 
 #include "../../include/p1hip.h"
+#include "async_slots.hpp"
 #include "batch_plan.hpp"
 #include "planner.hpp"
 #include "scan_abi.hpp"
@@ -250,6 +258,36 @@ struct Buf {
 template <typename T> using DevBuf = Buf<T, false>;
 template <typename T> using PinnedBuf = Buf<T, true>;
 
+// One device's buffers of one p1hip_batch_submit slot: everything a ticket's
+// launches read or write on this device, so that the next submit (another
+// slot) and the synchronous calls (the Dev's own buffers) never touch what an
+// outstanding ticket still uses.  The small and the wide route of one call
+// run back to back without a synchronisation, so they share nothing either.
+// Grown only by the submit that has just taken the slot, i.e. while it is idle.
+struct SlotDev {
+  // small route: every launch pair of the call at its own offset
+  DevBuf<BatchSeg> d_bseg;
+  PinnedBuf<BatchSeg> h_bseg;
+  DevBuf<uint32_t> d_btile0;
+  PinnedBuf<uint32_t> h_btile0;
+  DevBuf<Key> d_bout;
+  PinnedBuf<Key> h_bout;
+  DevBuf<Key> d_bpart;
+  // wide route
+  DevBuf<Key> d_part;
+  DevBuf<Segment> d_seg;
+  PinnedBuf<Segment> h_seg;
+  DevBuf<BatchSeg> d_gseg;
+  PinnedBuf<BatchSeg> h_gseg;
+  DevBuf<WideRange> d_wrange;
+  PinnedBuf<WideRange> h_wrange;
+  DevBuf<uint32_t> d_wrange0;
+  PinnedBuf<uint32_t> h_wrange0;
+  DevBuf<Key> d_wout;
+  PinnedBuf<Key> h_wout;
+  hipEvent_t done = nullptr;  // recorded after the ticket's last copy back (created on first use)
+};
+
 // Move-only (its buffers are): fine in std::vector<Dev> and for d = Dev().
 struct Dev {
   int ordinal = -1;
@@ -283,6 +321,7 @@ struct Dev {
   // and the ticket with p1hip_scan, d_bseg, d_btile0 and d_bout with the batch)
   DevBuf<WideRange> d_wrange;
   PinnedBuf<WideRange> h_wrange;
+  SlotDev slot[P1HIP_MAX_INFLIGHT];  // p1hip_batch_submit: one buffer set per ticket slot
   std::vector<hipEvent_t> evs;  // profiling event pool (pairs)
   // MODE 5 K+W tables on this device, least recently used first (built by
   // k_kwtable; keyed by the block-1 template and k)
@@ -300,8 +339,40 @@ struct Dev {
   p1hip_device_stats_t acc{};
 };
 
+// What p1hip_batch_wait needs of a submitted call (host memory only).
+struct AsyncCall {
+  size_t n = 0;
+  std::vector<p1hip_result_t> res;  // empty ranges are already answered
+  // where the coalesced results land: h_out[r] (pinned, the slot's) is request reqs[r]'s
+  struct Part {
+    const Key* h_out;
+    std::vector<size_t> reqs;
+  };
+  std::vector<Part> parts;
+  std::vector<char> dev_used;  // per device: the ticket recorded its event there
+  // individual-route requests, run by the wait (their messages are copies)
+  struct Indiv {
+    size_t idx;
+    std::string msg;
+    uint64_t lower, upper;
+  };
+  std::vector<Indiv> indiv;
+  // what the synchronous call would add to the statistics
+  bool has_b = false, has_w = false;
+  p1hip_batch_stats_t badd{};
+  p1hip_wide_stats_t wadd{};
+  double submit_ms = 0.0;
+};
+
 struct Runtime {
   std::mutex mu;
+  // p1hip_batch_submit / p1hip_batch_wait: the tickets, their calls, and the
+  // waits blocked on events with `mu` released (shutdown_locked waits for them)
+  AsyncSlotsT<P1HIP_MAX_INFLIGHT> slots;
+  AsyncCall calls[P1HIP_MAX_INFLIGHT];
+  std::condition_variable cv;
+  int blockers = 0;
+  p1hip_async_stats_t astats{};
   std::vector<Dev> devs;
   bool profiling = false;
   // the kAtInit knobs, as the open devices were opened with
@@ -402,6 +473,8 @@ int dev_release(Dev& d) {
   (void)hipSetDevice(d.ordinal);
   if (d.stream) (void)hipStreamSynchronize(d.stream);
   for (hipEvent_t e : d.evs) (void)hipEventDestroy(e);
+  for (SlotDev& sd : d.slot)
+    if (sd.done) (void)hipEventDestroy(sd.done);
   for (Dev::KwTab& t : d.kwtabs) (void)hipFree(t.dptr);
   if (d.comm) ncclCommDestroy(d.comm);
   if (d.stream) (void)hipStreamDestroy(d.stream);
@@ -411,7 +484,22 @@ int dev_release(Dev& d) {
   return 0;
 }
 
+// With R.mu held by the caller.  Outstanding tickets are cancelled; a
+// p1hip_batch_wait blocked on a ticket's events (with R.mu released) is let
+// out first -- the streams are drained, so its events complete -- because the
+// events and buffers it looks at are destroyed below.  It finds its ticket
+// stale when it takes the mutex again.
 void shutdown_locked(Runtime& R) {
+  R.slots.CancelAll();
+  if (R.blockers > 0) {
+    for (Dev& d : R.devs)
+      if (d.stream) (void)hipStreamSynchronize(d.stream);
+    std::unique_lock<std::mutex> lk(R.mu, std::adopt_lock);
+    R.cv.wait(lk, [&] { return R.blockers == 0; });
+    lk.release();  // still locked: the caller's guard owns it
+    R.slots.CancelAll();  // tickets issued while the mutex was released
+  }
+  for (AsyncCall& c : R.calls) c = AsyncCall();
   for (Dev& d : R.devs) dev_release(d);
   R.devs.clear();
 }
@@ -918,6 +1006,29 @@ int batch_reserve(Dev& d, size_t nseg, size_t nreq, size_t tiles) {
   return P1HIP_OK;
 }
 
+// The buffers one launch pair runs in: the Dev's own (the synchronous calls),
+// or a place in a ticket slot's (p1hip_batch_submit).
+struct BatchBufs {
+  BatchSeg *d_seg, *h_seg;
+  uint32_t *d_tile0, *h_tile0;
+  Key *d_out, *h_out, *d_part;
+};
+
+// Enqueue launch pair L (tables T) on device d's stream: the tables, k_batch_scan,
+// k_batch_reduce and the copy back.  No synchronisation.
+int batch_enqueue(Dev& d, const BatchLaunch& L, const BatchTable& T, const BatchBufs& b) {
+  const size_t nseg = T.segs.size(), nreq = L.reqs.size();
+  memcpy(b.h_seg, T.segs.data(), nseg * sizeof(BatchSeg));
+  memcpy(b.h_tile0, T.req_tile0.data(), (nreq + 1) * sizeof(uint32_t));
+  HIPCHK(hipMemcpyAsync(b.d_seg, b.h_seg, nseg * sizeof(BatchSeg), hipMemcpyHostToDevice, d.stream));
+  HIPCHK(hipMemcpyAsync(b.d_tile0, b.h_tile0, (nreq + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, d.stream));
+  HIPCHK(launch(d.f_bscan, L.tiles, kBlock, d.stream, (const BatchSeg*)b.d_seg, (uint32_t)nseg, b.d_part));
+  HIPCHK(launch(d.f_breduce, (uint32_t)nreq, kBlock, d.stream, (const Key*)b.d_part, (const uint32_t*)b.d_tile0,
+                b.d_out));
+  HIPCHK(hipMemcpyAsync(b.h_out, b.d_out, nreq * sizeof(Key), hipMemcpyDeviceToHost, d.stream));
+  return P1HIP_OK;
+}
+
 // One p1hip_scan_batch with R.mu held by the caller (p1hip_scan_batch;
 // p1hip_scan_batch_wide for its small requests).
 int scan_batch_held(Runtime& R, const p1hip_request_t* reqs, size_t n, p1hip_result_t* out) {
@@ -950,16 +1061,8 @@ int scan_batch_held(Runtime& R, const p1hip_request_t* reqs, size_t n, p1hip_res
         const size_t nseg = T.segs.size(), nreq = L->reqs.size();
         HIPCHK(hipSetDevice(d.ordinal));
         if ((rc = batch_reserve(d, nseg, nreq, L->tiles)) != P1HIP_OK) return rc;
-        memcpy(d.h_bseg.p, T.segs.data(), nseg * sizeof(BatchSeg));
-        memcpy(d.h_btile0.p, T.req_tile0.data(), (nreq + 1) * sizeof(uint32_t));
-        HIPCHK(hipMemcpyAsync(d.d_bseg.p, d.h_bseg.p, nseg * sizeof(BatchSeg), hipMemcpyHostToDevice, d.stream));
-        HIPCHK(hipMemcpyAsync(d.d_btile0.p, d.h_btile0.p, (nreq + 1) * sizeof(uint32_t), hipMemcpyHostToDevice,
-                              d.stream));
-        HIPCHK(launch(d.f_bscan, L->tiles, kBlock, d.stream, (const BatchSeg*)d.d_bseg.p, (uint32_t)nseg,
-                      d.d_bpart.p));
-        HIPCHK(launch(d.f_breduce, (uint32_t)nreq, kBlock, d.stream, (const Key*)d.d_bpart.p,
-                      (const uint32_t*)d.d_btile0.p, d.d_bout.p));
-        HIPCHK(hipMemcpyAsync(d.h_bout.p, d.d_bout.p, nreq * sizeof(Key), hipMemcpyDeviceToHost, d.stream));
+        const BatchBufs b = {d.d_bseg.p, d.h_bseg.p, d.d_btile0.p, d.h_btile0.p, d.d_bout.p, d.h_bout.p, d.d_bpart.p};
+        if ((rc = batch_enqueue(d, *L, T, b)) != P1HIP_OK) return rc;
         tiles += L->tiles;
         nonces += T.nonces;
       }
@@ -1041,42 +1144,60 @@ int wide_reserve(Dev& d, const WideDevice& D) {
 // k_batch_scan for the generic pieces, the k_scan launches back to back (the
 // ticket is zero between launches, as in a multi-launch p1hip_scan), the
 // per-request fold and the copy back.  No synchronisation.
-int wide_enqueue(Dev& d, const WideDevice& D) {
+// `b`: the buffers it runs in, the Dev's own (wide_reserve; the synchronous
+// call) or a ticket slot's (p1hip_batch_submit).  The work-queue ticket is the
+// device's in both cases: launches on one stream run in order.
+struct WideBufs {
+  Key* d_part;
+  Segment *d_seg, *h_seg;
+  BatchSeg *d_gseg, *h_gseg;
+  WideRange *d_range, *h_range;
+  uint32_t *d_range0, *h_range0;
+  Key *d_out, *h_out;
+};
+
+int wide_enqueue(Dev& d, const WideDevice& D, const WideBufs& b) {
   const size_t nreq = D.reqs.size();
-  HIPCHK(hipSetDevice(d.ordinal));
-  int rc = wide_reserve(d, D);
-  if (rc) return rc;
   // segment tables of all k_scan launches, back to back (W.first is the launch's offset)
   for (const WideLaunch& W : D.launches) {
-    const std::string err = wide_fill_launch(D, W, d.h_seg.p + W.first);
+    const std::string err = wide_fill_launch(D, W, b.h_seg + W.first);
     if (!err.empty()) return fail(P1HIP_ERR_ARGS, err);
   }
   if (!D.fast.empty())
-    HIPCHK(hipMemcpyAsync(d.d_seg.p, d.h_seg.p, D.fast.size() * sizeof(Segment), hipMemcpyHostToDevice, d.stream));
-  memcpy(d.h_wrange.p, D.ranges.data(), D.ranges.size() * sizeof(WideRange));
-  memcpy(d.h_btile0.p, D.req_range0.data(), (nreq + 1) * sizeof(uint32_t));
-  HIPCHK(hipMemcpyAsync(d.d_wrange.p, d.h_wrange.p, D.ranges.size() * sizeof(WideRange), hipMemcpyHostToDevice,
-                        d.stream));
-  HIPCHK(hipMemcpyAsync(d.d_btile0.p, d.h_btile0.p, (nreq + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, d.stream));
+    HIPCHK(hipMemcpyAsync(b.d_seg, b.h_seg, D.fast.size() * sizeof(Segment), hipMemcpyHostToDevice, d.stream));
+  memcpy(b.h_range, D.ranges.data(), D.ranges.size() * sizeof(WideRange));
+  memcpy(b.h_range0, D.req_range0.data(), (nreq + 1) * sizeof(uint32_t));
+  HIPCHK(hipMemcpyAsync(b.d_range, b.h_range, D.ranges.size() * sizeof(WideRange), hipMemcpyHostToDevice, d.stream));
+  HIPCHK(hipMemcpyAsync(b.d_range0, b.h_range0, (nreq + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, d.stream));
   if (D.gen_tiles) {
-    memcpy(d.h_bseg.p, D.gsegs.data(), D.gsegs.size() * sizeof(BatchSeg));
-    HIPCHK(hipMemcpyAsync(d.d_bseg.p, d.h_bseg.p, D.gsegs.size() * sizeof(BatchSeg), hipMemcpyHostToDevice, d.stream));
-    HIPCHK(launch(d.f_bscan, D.gen_tiles, kBlock, d.stream, (const BatchSeg*)d.d_bseg.p, (uint32_t)D.gsegs.size(),
-                  (Key*)(d.d_part.p + D.gen_tile0)));
+    memcpy(b.h_gseg, D.gsegs.data(), D.gsegs.size() * sizeof(BatchSeg));
+    HIPCHK(hipMemcpyAsync(b.d_gseg, b.h_gseg, D.gsegs.size() * sizeof(BatchSeg), hipMemcpyHostToDevice, d.stream));
+    HIPCHK(launch(d.f_bscan, D.gen_tiles, kBlock, d.stream, (const BatchSeg*)b.d_gseg, (uint32_t)D.gsegs.size(),
+                  (Key*)(b.d_part + D.gen_tile0)));
   }
   for (const WideLaunch& W : D.launches) {
 #ifdef P1_STATIC_GRID
-    HIPCHK(launch(d.f_scan, W.tiles, kBlock, d.stream, (const Segment*)(d.d_seg.p + W.first), (uint32_t)W.count,
-                  (Key*)(d.d_part.p + W.tile0)));
+    HIPCHK(launch(d.f_scan, W.tiles, kBlock, d.stream, (const Segment*)(b.d_seg + W.first), (uint32_t)W.count,
+                  (Key*)(b.d_part + W.tile0)));
 #else
-    HIPCHK(launch(d.f_scan, scan_grid_for(d, W.tiles), kBlock, d.stream, (const Segment*)(d.d_seg.p + W.first),
-                  (uint32_t)W.count, (Key*)(d.d_part.p + W.tile0), (uint32_t)W.tiles, d.d_scan_ticket.p));
+    HIPCHK(launch(d.f_scan, scan_grid_for(d, W.tiles), kBlock, d.stream, (const Segment*)(b.d_seg + W.first),
+                  (uint32_t)W.count, (Key*)(b.d_part + W.tile0), (uint32_t)W.tiles, d.d_scan_ticket.p));
 #endif
   }
-  HIPCHK(launch(d.f_wreduce, (uint32_t)nreq, kBlock, d.stream, (const Key*)d.d_part.p,
-                (const WideRange*)d.d_wrange.p, (const uint32_t*)d.d_btile0.p, d.d_bout.p));
-  HIPCHK(hipMemcpyAsync(d.h_bout.p, d.d_bout.p, nreq * sizeof(Key), hipMemcpyDeviceToHost, d.stream));
+  HIPCHK(launch(d.f_wreduce, (uint32_t)nreq, kBlock, d.stream, (const Key*)b.d_part, (const WideRange*)b.d_range,
+                (const uint32_t*)b.d_range0, b.d_out));
+  HIPCHK(hipMemcpyAsync(b.h_out, b.d_out, nreq * sizeof(Key), hipMemcpyDeviceToHost, d.stream));
   return P1HIP_OK;
+}
+
+// The synchronous call's: in the Dev's own buffers.
+int wide_enqueue(Dev& d, const WideDevice& D) {
+  HIPCHK(hipSetDevice(d.ordinal));
+  int rc = wide_reserve(d, D);
+  if (rc) return rc;
+  const WideBufs b = {d.d_part.p,   d.d_seg.p,    d.h_seg.p,    d.d_bseg.p, d.h_bseg.p, d.d_wrange.p,
+                      d.h_wrange.p, d.d_btile0.p, d.h_btile0.p, d.d_bout.p, d.h_bout.p};
+  return wide_enqueue(d, D, b);
 }
 
 int scan_batch_wide_locked(const p1hip_request_t* reqs, size_t n, p1hip_result_t* out) {
@@ -1159,6 +1280,298 @@ int scan_batch_wide_locked(const p1hip_request_t* reqs, size_t n, p1hip_result_t
   S.tiles += add.tiles;
   S.nonces += add.nonces;
   S.wall_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return P1HIP_OK;
+}
+
+// ----------------------------------------------------------------------------
+// p1hip_batch_submit / p1hip_batch_wait
+// ----------------------------------------------------------------------------
+// Lay the call out as the synchronous call would, enqueue its empty, small and
+// wide routes in slot `s`'s buffers and record one event per device used.
+// R.mu held; the slot is the caller's.  No synchronisation.
+int submit_enqueue(Runtime& R, int s, AsyncCall& C, const p1hip_request_t* reqs, size_t n, bool wide) {
+  const std::vector<BatchReq> q = batch_reqs(reqs, n);
+  const size_t nd = R.devs.size();
+  C.n = n;
+  C.res.assign(n, p1hip_result_t{~0ull, 0});
+  C.dev_used.assign(nd, 0);
+  auto individual = [&](size_t i) {
+    C.indiv.push_back({i, std::string((const char*)q[i].msg, q[i].len), q[i].lower, q[i].upper});
+  };
+  // The requests of the small route: all of them for p1hip_scan_batch; for
+  // the wide call its route-1 requests, as one batch (scan_batch_wide_locked).
+  std::vector<BatchReq> sq;
+  std::vector<size_t> sidx;
+  WideLayout W;
+  if (wide) {
+    const std::string lerr = wide_layout_held(R, q, (int)nd, W);
+    if (!lerr.empty()) return fail(P1HIP_ERR_ARGS, lerr);
+    for (size_t i = 0; i < n; ++i) {
+      if (W.route[i] == kWideRouteSmall) {
+        sq.push_back(q[i]);
+        sidx.push_back(i);
+      } else if (W.route[i] == kWideRouteIndividual) {
+        individual(i);
+      }
+    }
+    C.has_w = true;
+    C.wadd.requests = n;
+    C.wadd.empty = W.empty;
+    C.wadd.small = W.small;
+    C.wadd.wide = W.wide;
+    C.wadd.individual = W.individual;
+  } else {
+    sq = q;
+    for (size_t i = 0; i < n; ++i) sidx.push_back(i);
+  }
+  int rc;
+  if (!wide || W.small) {
+    const BatchLayout Y =
+        batch_layout(sq.data(), sq.size(), (int)nd, knob(kBatchMaxNoncesKnob), knob(kBatchMaxTilesKnob));
+    for (size_t j = 0; j < sq.size(); ++j)
+      if (sq[j].lower <= sq[j].upper && Y.tiles[j] == 0) individual(sidx[j]);
+    C.has_b = true;
+    C.badd.requests = sq.size();
+    C.badd.coalesced = Y.coalesced;
+    C.badd.individual = Y.individual;
+    C.badd.empty = Y.empty;
+    C.badd.launches = Y.launches.size();
+    // every launch pair of a device gets a place of its own in the slot's
+    // buffers (the synchronous call reuses one place and synchronises between
+    // the pairs), so the tables are built first and the room reserved once
+    std::vector<BatchTable> T(Y.launches.size());
+    struct Need {
+      size_t seg = 0, req = 0, tile0 = 0, tiles = 0;
+    };
+    std::vector<Need> need(nd);
+    for (size_t li = 0; li < Y.launches.size(); ++li) {
+      const BatchLaunch& L = Y.launches[li];
+      const std::string err = batch_build_table(sq.data(), L, T[li]);
+      if (!err.empty()) return fail(P1HIP_ERR_ARGS, err);
+      Need& N = need[(size_t)L.device];
+      N.seg += T[li].segs.size();
+      N.req += L.reqs.size();
+      N.tile0 += L.reqs.size() + 1;
+      N.tiles += L.tiles;
+      C.badd.tiles += L.tiles;
+      C.badd.nonces += T[li].nonces;
+    }
+    for (size_t dv = 0; dv < nd; ++dv) {
+      const Need& N = need[dv];
+      if (!N.req) continue;
+      Dev& d = R.devs[dv];
+      SlotDev& sd = d.slot[s];
+      HIPCHK(hipSetDevice(d.ordinal));
+      HIPCHK(sd.d_bseg.reserve(N.seg, 64));
+      HIPCHK(sd.h_bseg.reserve(N.seg, 64));
+      HIPCHK(sd.d_btile0.reserve(N.tile0, 64));
+      HIPCHK(sd.h_btile0.reserve(N.tile0, 64));
+      HIPCHK(sd.d_bout.reserve(N.req, 64));
+      HIPCHK(sd.h_bout.reserve(N.req, 64));
+      HIPCHK(sd.d_bpart.reserve(N.tiles, 1024));
+      Need at;
+      for (size_t li = 0; li < Y.launches.size(); ++li) {
+        const BatchLaunch& L = Y.launches[li];
+        if ((size_t)L.device != dv) continue;
+        const BatchBufs b = {sd.d_bseg.p + at.seg,     sd.h_bseg.p + at.seg, sd.d_btile0.p + at.tile0,
+                             sd.h_btile0.p + at.tile0, sd.d_bout.p + at.req, sd.h_bout.p + at.req,
+                             sd.d_bpart.p + at.tiles};
+        if ((rc = batch_enqueue(d, L, T[li], b)) != P1HIP_OK) return rc;
+        C.dev_used[dv] = 1;
+        AsyncCall::Part P;
+        P.h_out = b.h_out;
+        for (size_t r : L.reqs) P.reqs.push_back(sidx[r]);
+        C.parts.push_back(std::move(P));
+        at.seg += T[li].segs.size();
+        at.req += L.reqs.size();
+        at.tile0 += L.reqs.size() + 1;
+        at.tiles += L.tiles;
+      }
+    }
+  }
+  if (wide)
+    for (size_t dv = 0; dv < W.devs.size(); ++dv) {
+      const WideDevice& D = W.devs[dv];
+      if (D.reqs.empty()) continue;
+      Dev& d = R.devs[dv];
+      SlotDev& sd = d.slot[s];
+      const size_t nreq = D.reqs.size();
+      HIPCHK(hipSetDevice(d.ordinal));
+      HIPCHK(sd.d_part.reserve(D.total_tiles, 1024));
+      HIPCHK(sd.d_seg.reserve(D.fast.size(), 4 * kMaxSegs));
+      HIPCHK(sd.h_seg.reserve(D.fast.size(), 4 * kMaxSegs));
+      HIPCHK(sd.d_gseg.reserve(D.gsegs.size(), 64));
+      HIPCHK(sd.h_gseg.reserve(D.gsegs.size(), 64));
+      HIPCHK(sd.d_wrange.reserve(D.ranges.size(), 64));
+      HIPCHK(sd.h_wrange.reserve(D.ranges.size(), 64));
+      HIPCHK(sd.d_wrange0.reserve(nreq, 64, 1));
+      HIPCHK(sd.h_wrange0.reserve(nreq, 64, 1));
+      HIPCHK(sd.d_wout.reserve(nreq, 64));
+      HIPCHK(sd.h_wout.reserve(nreq, 64));
+      const WideBufs b = {sd.d_part.p,   sd.d_seg.p,     sd.h_seg.p,     sd.d_gseg.p, sd.h_gseg.p, sd.d_wrange.p,
+                          sd.h_wrange.p, sd.d_wrange0.p, sd.h_wrange0.p, sd.d_wout.p, sd.h_wout.p};
+      if ((rc = wide_enqueue(d, D, b)) != P1HIP_OK) return rc;
+      C.dev_used[dv] = 1;
+      C.parts.push_back({sd.h_wout.p, D.reqs});
+      C.wadd.scan_launches += D.launches.size();
+      C.wadd.scan_segments += D.fast.size();
+      C.wadd.generic_launches += D.gen_tiles ? 1 : 0;
+      C.wadd.generic_segments += D.gsegs.size();
+      C.wadd.tiles += D.total_tiles;
+      C.wadd.nonces += D.nonces;
+    }
+  // one event per device, after the last copy back
+  for (size_t dv = 0; dv < nd; ++dv) {
+    if (!C.dev_used[dv]) continue;
+    Dev& d = R.devs[dv];
+    SlotDev& sd = d.slot[s];
+    HIPCHK(hipSetDevice(d.ordinal));
+    if (!sd.done) HIPCHK(hipEventCreate(&sd.done));
+    HIPCHK(hipEventRecord(sd.done, d.stream));
+  }
+  return P1HIP_OK;
+}
+
+void drain_streams(Runtime& R) {
+  const std::string keep = g_err;
+  for (Dev& d : R.devs)
+    if (d.stream) (void)hipStreamSynchronize(d.stream);
+  g_err = keep;
+}
+
+int batch_submit_locked(const p1hip_request_t* reqs, size_t n, bool wide, p1hip_ticket_t* ticket) {
+  Runtime& R = rt();
+  std::lock_guard<std::mutex> g(R.mu);
+  const auto t0 = std::chrono::steady_clock::now();
+  if (R.slots.Outstanding() >= P1HIP_MAX_INFLIGHT) {
+    R.astats.busy++;
+    return fail(P1HIP_ERR_BUSY, "P1HIP_MAX_INFLIGHT tickets are outstanding: wait for one first");
+  }
+  int rc = n ? ensure_init(R) : P1HIP_OK;
+  if (rc) return rc;
+  const uint64_t t = R.slots.Alloc();
+  const int s = R.slots.Holds(t);
+  AsyncCall& C = R.calls[s];
+  C = AsyncCall();
+  // a failure (or a host exception) after the first enqueue leaves nothing
+  // in flight in the slot's buffers and no ticket
+  auto abandon = [&] {
+    drain_streams(R);
+    C = AsyncCall();
+    R.slots.Release(t);
+  };
+  try {
+    rc = n ? submit_enqueue(R, s, C, reqs, n, wide) : P1HIP_OK;
+  } catch (...) {
+    abandon();
+    throw;
+  }
+  if (rc != P1HIP_OK) {
+    abandon();
+    return rc;
+  }
+  C.submit_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  R.astats.submits++;
+  R.astats.submit_ms += C.submit_ms;
+  R.astats.max_inflight = std::max<uint64_t>(R.astats.max_inflight, (uint64_t)R.slots.Outstanding());
+  *ticket = t;
+  return P1HIP_OK;
+}
+
+int batch_wait_locked(p1hip_ticket_t ticket, p1hip_result_t* out) {
+  Runtime& R = rt();
+  std::unique_lock<std::mutex> lk(R.mu);
+  const auto t0 = std::chrono::steady_clock::now();
+  const int s = R.slots.Claim(ticket);
+  if (s < 0) return fail(P1HIP_ERR_ARGS, "ticket is unknown, already waited or cancelled");
+  AsyncCall& C = R.calls[s];
+  // Block on the ticket's events with the mutex released: other threads
+  // submit, wait and scan meanwhile.  The slot is claimed, so nobody reuses
+  // its buffers, and shutdown_locked lets this thread out before it destroys
+  // the events.
+  std::vector<hipEvent_t> evs;
+  for (size_t dv = 0; dv < C.dev_used.size() && dv < R.devs.size(); ++dv)
+    if (C.dev_used[dv]) evs.push_back(R.devs[dv].slot[s].done);
+  hipError_t werr = hipSuccess;
+  if (!evs.empty()) {
+    R.blockers++;
+    lk.unlock();
+    for (hipEvent_t e : evs) {
+      const hipError_t x = hipEventSynchronize(e);
+      if (werr == hipSuccess) werr = x;
+    }
+    lk.lock();
+    R.blockers--;
+    R.cv.notify_all();
+  }
+  if (R.slots.Holds(ticket) != s) return fail(P1HIP_ERR_ARGS, "ticket was cancelled by p1hip_shutdown or a re-init");
+  auto finish = [&]() -> int {
+    if (werr != hipSuccess) return fail(P1HIP_ERR_HIP, std::string("hipEventSynchronize: ") + hipGetErrorString(werr));
+    if (C.n && !out) return fail(P1HIP_ERR_ARGS, "null result array");
+    for (const AsyncCall::Part& P : C.parts)
+      for (size_t r = 0; r < P.reqs.size(); ++r) {
+        const Key kq = finish_key(P.h_out[r]);
+        C.res[P.reqs[r]] = p1hip_result_t{kq.h, kq.n};
+      }
+    // individual route: one by one through the multi-device scan path
+    for (const AsyncCall::Indiv& I : C.indiv) {
+      const int rc = scan_held(R, (const uint8_t*)I.msg.data(), I.msg.size(), I.lower, I.upper, &C.res[I.idx].hash,
+                               &C.res[I.idx].nonce);
+      if (rc) return fail(rc, "request " + std::to_string(I.idx) + ": " + g_err);
+    }
+    return P1HIP_OK;
+  };
+  // the ticket is spent and the slot free again, whatever happens
+  auto release = [&] {
+    C = AsyncCall();
+    R.slots.Release(ticket);
+  };
+  int rc;
+  try {
+    rc = finish();
+  } catch (...) {
+    drain_streams(R);
+    release();
+    throw;
+  }
+  if (rc != P1HIP_OK) {
+    drain_streams(R);  // the slot's buffers are idle before the next submit takes them
+    release();
+    return rc;
+  }
+  for (size_t i = 0; i < C.n; ++i) out[i] = C.res[i];
+  const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  if (C.has_b) {
+    p1hip_batch_stats_t& S = R.bstats;
+    S.calls++;
+    S.requests += C.badd.requests;
+    S.coalesced += C.badd.coalesced;
+    S.individual += C.badd.individual;
+    S.empty += C.badd.empty;
+    S.launches += C.badd.launches;
+    S.tiles += C.badd.tiles;
+    S.nonces += C.badd.nonces;
+    if (!C.has_w) S.wall_ms += C.submit_ms + ms;
+  }
+  if (C.has_w) {
+    p1hip_wide_stats_t& S = R.wstats;
+    S.calls++;
+    S.requests += C.wadd.requests;
+    S.empty += C.wadd.empty;
+    S.small += C.wadd.small;
+    S.wide += C.wadd.wide;
+    S.individual += C.wadd.individual;
+    S.scan_launches += C.wadd.scan_launches;
+    S.scan_segments += C.wadd.scan_segments;
+    S.generic_launches += C.wadd.generic_launches;
+    S.generic_segments += C.wadd.generic_segments;
+    S.tiles += C.wadd.tiles;
+    S.nonces += C.wadd.nonces;
+    S.wall_ms += C.submit_ms + ms;
+  }
+  R.astats.waits++;
+  R.astats.wait_ms += ms;
+  release();
   return P1HIP_OK;
 }
 
@@ -1406,6 +1819,27 @@ int p1hip_get_wide_stats(p1hip_wide_stats_t* out) {
   return P1HIP_OK;
 }
 
+int p1hip_batch_submit(const p1hip_request_t* reqs, size_t n, int wide, p1hip_ticket_t* ticket) {
+  if (!ticket) return fail(P1HIP_ERR_ARGS, "null ticket pointer");
+  if (n && !reqs) return fail(P1HIP_ERR_ARGS, "null request array");
+  return guarded([&]() {
+    const int rc = batch_check(reqs, n);
+    return rc ? rc : batch_submit_locked(reqs, n, wide != 0, ticket);
+  });
+}
+
+int p1hip_batch_wait(p1hip_ticket_t ticket, p1hip_result_t* out) {
+  return guarded([&]() { return batch_wait_locked(ticket, out); });
+}
+
+int p1hip_get_async_stats(p1hip_async_stats_t* out) {
+  if (!out) return fail(P1HIP_ERR_ARGS, "null stats pointer");
+  Runtime& R = rt();
+  std::lock_guard<std::mutex> g(R.mu);
+  *out = R.astats;
+  return P1HIP_OK;
+}
+
 int p1hip_plan_shards(const uint8_t* msg, size_t msg_len, uint64_t lower, uint64_t upper, int n,
                       uint64_t* first, uint64_t* last) {
   if (n <= 0 || !first || !last) return fail(P1HIP_ERR_ARGS, "n <= 0 or null output");
@@ -1453,6 +1887,7 @@ void p1hip_reset_stats(void) {
   R.stats = p1hip_stats_t{};
   R.bstats = p1hip_batch_stats_t{};
   R.wstats = p1hip_wide_stats_t{};
+  R.astats = p1hip_async_stats_t{};
   for (Dev& d : R.devs) {
     d.acc = p1hip_device_stats_t{};
     d.acc.shard_first = 1;  // empty until the next scan

@@ -104,4 +104,25 @@ void AnswerPieces(const std::vector<Piece>& pieces, bool wide, std::vector<Piece
   }
 }
 
+uint64_t SubmitPieces(const std::vector<Piece>& pieces, bool wide) {
+  std::vector<p1hip_request_t> q;
+  q.reserve(pieces.size());
+  for (const Piece& p : pieces)
+    q.push_back({reinterpret_cast<const uint8_t*>(p.msg.data()), p.msg.size(), p.lower, p.upper});
+  p1hip_ticket_t t = 0;
+  const int rc = p1hip_batch_submit(q.data(), q.size(), wide ? 1 : 0, &t);  // the messages are borrowed until it returns
+  if (rc != P1HIP_OK) throw bitcoin::HipError(rc, std::string("p1hip_batch_submit: ") + p1hip_last_error());
+  return t;
+}
+
+void CollectPieces(uint64_t handle, std::vector<PieceResult>* out) {
+  std::vector<p1hip_result_t> res(out->size());
+  const int rc = p1hip_batch_wait(handle, res.data());
+  if (rc != P1HIP_OK) throw bitcoin::HipError(rc, std::string("p1hip_batch_wait: ") + p1hip_last_error());
+  for (size_t i = 0; i < res.size(); ++i) {
+    (*out)[i].hash = res[i].hash;
+    (*out)[i].nonce = res[i].nonce;
+  }
+}
+
 }  // namespace miner

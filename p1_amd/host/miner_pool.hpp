@@ -156,6 +156,12 @@ class Rounds {
     return n;
   }
   bool HasDone() const { return !done_.empty(); }
+  // Connections whose active job has no piece in flight: what Next would cut.
+  size_t Free() const {
+    size_t n = 0;
+    for (const auto& kv : conns_) n += !kv.second.q.empty() && !kv.second.q.front().inflight;
+    return n;
+  }
 
  private:
   struct Job {
@@ -182,6 +188,91 @@ class Rounds {
   uint64_t serial_ = 0;
 };
 
+// Rounds in flight.  A backend that can take a round and answer it later
+// (AsyncBackend: Submit now, Collect when it is needed) lets the pool cut and
+// submit round k + 1 while round k runs.  Pipeline holds the rounds that are
+// out, oldest first, and the one decision of the round loop: with fewer than
+// `depth` rounds out and Rounds::Next non-empty, cut and submit another;
+// otherwise collect the oldest, fold it (Rounds::Finish) and hand back the
+// finished jobs.  Rounds needs no change for this: Next skips a job whose
+// piece is in flight, so a job has at most one piece outstanding over all the
+// rounds that are out, and its pieces still fold in increasing nonce order.
+// No threads, no I/O (tests/pool_pipeline_test.cpp); RunPool calls the parts
+// with its own locking, single-threaded users call Step.
+class Pipeline {
+ public:
+  struct Round {
+    uint64_t index = 0;  // rounds submitted before this one
+    std::vector<Piece> pieces;
+    uint64_t handle = 0;  // the backend's
+  };
+
+  explicit Pipeline(size_t depth) : depth_(depth ? depth : 1) {}
+
+  size_t Depth() const { return depth_; }
+  size_t Outstanding() const { return out_.size(); }
+  size_t MaxOutstanding() const { return max_out_; }
+  uint64_t Submitted() const { return submitted_; }
+  const Round& Oldest() const { return out_.front(); }
+
+  // The next round's pieces, or none: `depth` rounds are out already, or no
+  // active job is free (Rounds::Next).  A non-empty result must be submitted
+  // and reported with Sent (its jobs are marked in flight).
+  std::vector<Piece> Cut(Rounds& rounds, uint64_t chunk) {
+    if (out_.size() >= depth_) return {};
+    return rounds.Next(chunk);
+  }
+
+  // The pieces of Cut went to the backend, which knows them as `handle`.
+  const Round& Sent(std::vector<Piece> pieces, uint64_t handle) {
+    Round r;
+    r.index = submitted_++;
+    r.pieces = std::move(pieces);
+    r.handle = handle;
+    out_.push_back(std::move(r));
+    if (out_.size() > max_out_) max_out_ = out_.size();
+    return out_.back();
+  }
+
+  // The backend answered the oldest round: fold it and return the jobs this finished.
+  std::vector<Done> Collected(Rounds& rounds, const std::vector<PieceResult>& results) {
+    std::vector<Done> d = rounds.Finish(out_.front().pieces, results);
+    out_.pop_front();
+    return d;
+  }
+
+  // Forget the oldest round without folding it (a backend that failed; shutdown).
+  void Abandon() { out_.pop_front(); }
+
+  // The decision, for a caller without locks: kSubmitted (another round went
+  // out), kCollected (the oldest came back; *done: the jobs it finished) or
+  // kIdle (nothing out and nothing to cut).  B has
+  //   uint64_t Submit(const std::vector<Piece>&)
+  //   void Collect(uint64_t handle, std::vector<PieceResult>* results)   (sized to the round)
+  enum Action { kIdle, kSubmitted, kCollected };
+  template <typename B>
+  Action Step(Rounds& rounds, B& backend, uint64_t chunk, std::vector<Done>* done) {
+    std::vector<Piece> pieces = Cut(rounds, chunk);
+    if (!pieces.empty()) {
+      const uint64_t h = backend.Submit(pieces);
+      Sent(std::move(pieces), h);
+      return kSubmitted;
+    }
+    if (out_.empty()) return kIdle;
+    std::vector<PieceResult> res(out_.front().pieces.size());
+    backend.Collect(out_.front().handle, &res);
+    std::vector<Done> d = Collected(rounds, res);
+    if (done) done->insert(done->end(), d.begin(), d.end());
+    return kCollected;
+  }
+
+ private:
+  size_t depth_;
+  std::deque<Round> out_;
+  size_t max_out_ = 0;
+  uint64_t submitted_ = 0;
+};
+
 struct PoolStats {
   uint64_t conns_wanted = 0;  // --conns
   uint64_t conns_open = 0;    // ... that joined the server
@@ -190,18 +281,20 @@ struct PoolStats {
   uint64_t rounds = 0;        // backend calls
   uint64_t max_round = 0;     // most pieces in one round
   uint64_t lost_conns = 0;    // connections whose Read or Write failed
+  uint64_t inflight = 1;      // --inflight: rounds that may be outstanding at once
+  uint64_t max_outstanding = 0;  // most rounds outstanding at once
 };
 
 // "conns_wanted": .., ... "lost_conns": ..  -- the members of a JSON object,
 // without its braces (p1miner adds the library's statistics after them).
 inline std::string StatsJsonFields(const PoolStats& s) {
-  char b[320];
+  char b[480];
   snprintf(b, sizeof b,
            "\"conns_wanted\": %llu, \"conns_open\": %llu, \"requests\": %llu, \"pieces\": %llu, \"rounds\": %llu, "
-           "\"max_round\": %llu, \"lost_conns\": %llu",
+           "\"max_round\": %llu, \"lost_conns\": %llu, \"inflight\": %llu, \"max_outstanding\": %llu",
            (unsigned long long)s.conns_wanted, (unsigned long long)s.conns_open, (unsigned long long)s.requests,
            (unsigned long long)s.pieces, (unsigned long long)s.rounds, (unsigned long long)s.max_round,
-           (unsigned long long)s.lost_conns);
+           (unsigned long long)s.lost_conns, (unsigned long long)s.inflight, (unsigned long long)s.max_outstanding);
   return b;
 }
 
@@ -212,6 +305,22 @@ using PoolBackend = std::function<void(const std::vector<Piece>&, std::vector<Pi
 // through one p1hip_scan_batch call, or one p1hip_scan_batch_wide call with
 // `wide`.  Throws bitcoin::HipError.
 void AnswerPieces(const std::vector<Piece>& pieces, bool wide, std::vector<PieceResult>* out);
+
+// The second backend shape, for --inflight N >= 2: Submit hands a round over
+// and returns at once with a handle; Collect blocks until that round is done
+// and fills one result per piece (`results` comes sized to the round).
+// Submit is called from the round loop's thread, Collect from one other
+// thread (the collector), in Submit's order.
+struct AsyncBackend {
+  std::function<uint64_t(const std::vector<Piece>&)> Submit;
+  std::function<void(uint64_t, std::vector<PieceResult>*)> Collect;
+};
+
+// The GPU one (miner_gpu.cpp): p1hip_batch_submit(..., wide) and
+// p1hip_batch_wait; the handle is the ticket.  They copy nothing more than
+// AnswerPieces does.  Throw bitcoin::HipError.
+uint64_t SubmitPieces(const std::vector<Piece>& pieces, bool wide);
+void CollectPieces(uint64_t handle, std::vector<PieceResult>* out);
 
 namespace pool_detail {
 // SIGTERM / SIGINT end the pool: the handler only writes to an eventfd, a
@@ -246,10 +355,24 @@ inline void on_signal(int) {
 // round_log (if not empty): one appended text line per round, the round's
 // index and then conn:lower:upper for each of its pieces.
 // An exception of the backend ends the pool the same way and is rethrown.
-inline int RunPool(const std::string& hostport, const lsp::Params& params, int conns, uint64_t chunk, long linger_us,
-                   const PoolBackend& backend, const std::string& round_log, PoolStats* stats,
-                   std::string* err = nullptr) {
+//
+// With `async` and inflight >= 2 the loop keeps up to `inflight` rounds
+// outstanding (Pipeline): it cuts and submits a round whenever fewer are out
+// and a job is free, and answers finished jobs and writes the round log while
+// the backend works; it never blocks in the backend.  One more thread, the
+// collector, blocks in Collect for the oldest round and folds it.  A round's
+// log line is written when it is submitted.  --linger-us applies before a
+// round is cut while nothing is outstanding.  On shutdown, when every
+// connection is lost and after a backend exception every outstanding round is
+// collected (its results ignored) before the clients are closed.  With inflight <= 1 `backend` is used and the loop
+// is the synchronous one, call for call.
+namespace pool_detail {
+inline int RunPoolImpl(const std::string& hostport, const lsp::Params& params, int conns, uint64_t chunk,
+                       long linger_us, const PoolBackend* backend_p, const AsyncBackend* async, int inflight,
+                       const std::string& round_log, PoolStats* stats, std::string* err) {
   PoolStats st;
+  const bool pipelined = async && inflight >= 2;
+  st.inflight = pipelined ? (uint64_t)inflight : 1;
   st.conns_wanted = (uint64_t)(conns > 0 ? conns : 0);
   std::vector<std::unique_ptr<lsp::Client>> clis;
   std::string first_err;
@@ -338,7 +461,103 @@ inline int RunPool(const std::string& hostport, const lsp::Params& params, int c
   };
 
   std::exception_ptr failure;
-  try {
+  Pipeline pipe(pipelined ? (size_t)inflight : 1);
+  // Pipelined: the round loop never blocks in the backend.  A collector
+  // thread waits for the oldest round (Collect), folds it under `mu` and
+  // leaves the finished jobs in `carry`; the round loop cuts and submits a
+  // round whenever fewer than `inflight` are out and a job is free
+  // (Rounds::Free), and writes Results meanwhile.
+  std::vector<Done> carry;      // finished by the collector, not yet written (mu)
+  bool collector_quit = false;  // mu
+  std::exception_ptr collect_failure;  // mu
+  std::thread collector;
+  if (pipelined) collector = std::thread([&] {
+    std::unique_lock<std::mutex> lk(mu);
+    for (;;) {
+      cv.wait(lk, [&] { return collector_quit || pipe.Outstanding() > 0; });
+      if (pipe.Outstanding() == 0) return;  // quit, and nothing left out
+      const uint64_t handle = pipe.Oldest().handle;
+      std::vector<PieceResult> res(pipe.Oldest().pieces.size());
+      lk.unlock();
+      std::exception_ptr ex;
+      try {
+        async->Collect(handle, &res);
+      } catch (...) {
+        ex = std::current_exception();
+      }
+      lk.lock();
+      if (ex) {  // the round is abandoned; the round loop ends the pool
+        if (!collect_failure) collect_failure = ex;
+        pipe.Abandon();
+      } else {
+        std::vector<Done> d = pipe.Collected(rounds, res);
+        st.requests += d.size();
+        carry.insert(carry.end(), d.begin(), d.end());
+      }
+      cv.notify_all();
+    }
+  });
+  if (pipelined) try {
+    std::unique_lock<std::mutex> lk(mu);
+    for (;;) {
+      cv.wait(lk, [&] {
+        return stop || alive == 0 || collect_failure || !carry.empty() || rounds.HasDone() ||
+               (pipe.Outstanding() < pipe.Depth() && rounds.Free() > 0);
+      });
+      if (stop || alive == 0 || collect_failure) {
+        std::vector<Done> last;
+        last.swap(carry);
+        lk.unlock();
+        answer(last);
+        lk.lock();
+        break;
+      }
+      if (linger_us > 0 && pipe.Outstanding() == 0 && rounds.Active() < alive)
+        cv.wait_for(lk, std::chrono::microseconds(linger_us),
+                    [&] { return stop || alive == 0 || rounds.Active() >= alive; });
+      std::vector<Done> done = rounds.TakeDone();
+      st.requests += done.size();
+      done.insert(done.end(), carry.begin(), carry.end());
+      carry.clear();
+      std::vector<Piece> pieces = pipe.Cut(rounds, chunk);
+      lk.unlock();
+      if (!pieces.empty()) {
+        if (logf) {
+          fprintf(logf, "%llu", (unsigned long long)st.rounds);
+          for (const Piece& p : pieces)
+            fprintf(logf, " %d:%llu:%llu", p.conn, (unsigned long long)p.lower, (unsigned long long)p.upper);
+          fputc('\n', logf);
+          fflush(logf);
+        }
+        ++st.rounds;
+        st.pieces += pieces.size();
+        if (pieces.size() > st.max_round) st.max_round = pieces.size();
+        const uint64_t h = async->Submit(pieces);
+        lk.lock();
+        pipe.Sent(std::move(pieces), h);
+        st.max_outstanding = pipe.MaxOutstanding();
+        cv.notify_all();  // the collector
+        lk.unlock();
+      }
+      answer(done);  // while the backend works
+      lk.lock();
+    }
+  } catch (...) {
+    failure = std::current_exception();
+  }
+  if (pipelined) {
+    // nothing stays outstanding behind the pool: the collector takes what is
+    // out (a Submit that threw left its pieces marked in flight, nothing out)
+    {
+      std::lock_guard<std::mutex> g(mu);
+      collector_quit = true;
+    }
+    cv.notify_all();
+    collector.join();
+    if (!failure) failure = collect_failure;
+  }
+  else try {
+    const PoolBackend& backend = *backend_p;
     std::unique_lock<std::mutex> lk(mu);
     for (;;) {
       cv.wait(lk, [&] { return stop || alive == 0 || rounds.Active() > 0 || rounds.HasDone(); });
@@ -364,6 +583,7 @@ inline int RunPool(const std::string& hostport, const lsp::Params& params, int c
         lk.lock();
         done = rounds.Finish(pieces, res);
         ++st.rounds;
+        st.max_outstanding = 1;
         st.pieces += pieces.size();
         if (pieces.size() > st.max_round) st.max_round = pieces.size();
         st.requests += done.size();
@@ -396,6 +616,22 @@ inline int RunPool(const std::string& hostport, const lsp::Params& params, int c
   if (stats) *stats = st;
   if (failure) std::rethrow_exception(failure);
   return 0;
+}
+}  // namespace pool_detail
+
+inline int RunPool(const std::string& hostport, const lsp::Params& params, int conns, uint64_t chunk, long linger_us,
+                   const PoolBackend& backend, const std::string& round_log, PoolStats* stats,
+                   std::string* err = nullptr) {
+  return pool_detail::RunPoolImpl(hostport, params, conns, chunk, linger_us, &backend, nullptr, 1, round_log, stats,
+                                  err);
+}
+
+// RunPool with up to `inflight` rounds outstanding (1: the loop above, through `backend`).
+inline int RunPool(const std::string& hostport, const lsp::Params& params, int conns, uint64_t chunk, long linger_us,
+                   const PoolBackend& backend, const AsyncBackend& async, int inflight, const std::string& round_log,
+                   PoolStats* stats, std::string* err = nullptr) {
+  return pool_detail::RunPoolImpl(hostport, params, conns, chunk, linger_us, &backend, &async, inflight, round_log,
+                                  stats, err);
 }
 
 }  // namespace miner

@@ -10,7 +10,7 @@
 //                                        this thread while the LSP event loop
 //                                        keeps heartbeating, so a long GPU job
 //                                        never trips the epoch limit.
-//   p1miner lsp <host:port> --conns C [--wide] [--linger-us U] [--round-log FILE]
+//   p1miner lsp <host:port> --conns C [--wide] [--linger-us U] [--round-log FILE] [--inflight N]
 //           [--stats] [the flags above]  one process, C connections (1..256),
 //                                        each a miner to the server; their jobs
 //                                        are answered in rounds, one piece of at
@@ -23,7 +23,13 @@
 //                                        round (default 0).  --round-log FILE:
 //                                        one line per round, its index and then
 //                                        conn:lower:upper per piece.  --stats:
-//                                        one JSON line on stdout at exit.  Ends
+//                                        one JSON line on stdout at exit.
+//                                        --inflight N (1..4, default 1): up to
+//                                        N rounds outstanding, each through
+//                                        p1hip_batch_submit / p1hip_batch_wait,
+//                                        so the next round is cut and submitted
+//                                        and Results are written while the GPU
+//                                        runs the last one.  Ends
 //                                        when every connection is lost, or on
 //                                        SIGTERM / SIGINT.
 //
@@ -78,7 +84,7 @@ static int usage() {
           "usage: p1miner scan <msg> <lower> <upper> | hash <msg> <nonce> | "
           "serve [--device N] [--chunk C] [--batch B [--wide]] | lsp <host:port> [--device N] [--chunk C] [--epoch-limit K] "
           "[--epoch-millis M] [--window W] [--copies K] [--connect-copies K] "
-          "[--conns C [--wide] [--linger-us U] [--round-log FILE] [--stats]] | json | lsp-json | lsp-wrap <connID> <seq> | lsp-unwrap\n");
+          "[--conns C [--wide] [--linger-us U] [--round-log FILE] [--stats] [--inflight N]] | json | lsp-json | lsp-wrap <connID> <seq> | lsp-unwrap\n");
   return 2;
 }
 
@@ -95,15 +101,18 @@ static bool parse_u64(const char* s, uint64_t* v) {
 // p1miner lsp --conns C: the GPU is open; run the pool (miner_pool.hpp) over
 // miner::AnswerPieces, print the statistics, release the GPU.
 static int run_pool(const std::string& hostport, const lsp::Params& prm, int conns, uint64_t chunk, long linger_us,
-                    bool wide, const std::string& round_log, bool want_stats) {
+                    bool wide, int inflight, const std::string& round_log, bool want_stats) {
   miner::PoolStats st;
   std::string err;
+  miner::AsyncBackend async;
+  async.Submit = [wide](const std::vector<miner::Piece>& pieces) { return miner::SubmitPieces(pieces, wide); };
+  async.Collect = [](uint64_t h, std::vector<miner::PieceResult>* out) { miner::CollectPieces(h, out); };
   const int rc = miner::RunPool(
       hostport, prm, conns, chunk, linger_us,
       [wide](const std::vector<miner::Piece>& pieces, std::vector<miner::PieceResult>* out) {
         miner::AnswerPieces(pieces, wide, out);
       },
-      round_log, &st, &err);
+      async, inflight, round_log, &st, &err);
   if (rc != 0) {
     printf("Failed to join with server: %s\n", err.c_str());
     return 1;
@@ -133,13 +142,14 @@ static int run_lsp(int argc, char** argv) {
   const std::string hostport = argv[2];
   int dev = -1;
   uint64_t chunk = miner::kDefaultChunk;
-  uint64_t conns = 0, linger_us = 0;
+  uint64_t conns = 0, linger_us = 0, inflight = 1;
   bool wide = false, want_stats = false;
   std::string round_log;
   lsp::Params prm = lsp::NewParams();
   prm.Copies = lsp::DefaultAppCopies;
   for (int i = 3; i < argc; ++i) {
     if (!strcmp(argv[i], "--device") && i + 1 < argc) dev = atoi(argv[++i]);
+    else if (!strcmp(argv[i], "--inflight") && i + 1 < argc) { if (!parse_u64(argv[++i], &inflight) || inflight < 1 || inflight > P1HIP_MAX_INFLIGHT) return usage(); }
     else if (!strcmp(argv[i], "--conns") && i + 1 < argc) { if (!parse_u64(argv[++i], &conns) || conns < 1 || conns > 256) return usage(); }
     else if (!strcmp(argv[i], "--linger-us") && i + 1 < argc) { if (!parse_u64(argv[++i], &linger_us) || linger_us > 60000000) return usage(); }
     else if (!strcmp(argv[i], "--round-log") && i + 1 < argc) round_log = argv[++i];
@@ -154,12 +164,12 @@ static int run_lsp(int argc, char** argv) {
     else return usage();
   }
   // the pool's flags mean nothing to the single-connection loop
-  if (conns == 0 && (wide || want_stats || linger_us || !round_log.empty())) return usage();
+  if (conns == 0 && (wide || want_stats || linger_us || inflight != 1 || !round_log.empty())) return usage();
   // open the GPU before joining, so the first request does not pay for it
   int rc = dev >= 0 ? p1hip_init_devices(&dev, 1) : p1hip_init(0, nullptr);
   if (rc != P1HIP_OK) { fprintf(stderr, "p1hip init: %s\n", p1hip_last_error()); return 1; }
   std::string err;
-  if (conns) return run_pool(hostport, prm, (int)conns, chunk, (long)linger_us, wide, round_log, want_stats);
+  if (conns) return run_pool(hostport, prm, (int)conns, chunk, (long)linger_us, wide, (int)inflight, round_log, want_stats);
   std::unique_ptr<lsp::Client> cli = lsp::NewClient(hostport, prm, &err);
   if (!cli) {
     printf("Failed to join with server: %s\n", err.c_str());

@@ -7,6 +7,8 @@ after the Result of the one before), answered by
   a  8 x `p1miner lsp`                 one process per miner slot (configs[4]'s arrangement)
   b  1 x `p1miner lsp --conns 8 --wide`
   c  1 x `p1miner lsp --conns 64 --wide`
+  d  1 x `p1miner lsp --conns 64 --wide --inflight N`   (only with --inflight N, N >= 2:
+     up to N rounds outstanding through p1hip_batch_submit / p1hip_batch_wait)
 Every client's first job warms the miners and is not timed (lsp_load --warm 1,
 on the same connections: a second lsp_load process could be handed the UDP
 port, and with it the server-side connection, of a client the first one just
@@ -19,7 +21,8 @@ as one JSON line.
 env: SIZES (10000,100000,1000000,10000000), CLIENTS (64), JOBS (20),
      DEVICE (0), OUT (profiles/pool_bench.json), CELL_TIMEOUT (120);
      FAKE=1 runs the CPU oracle-backed doubles (tools/lsp_fake_miner,
-     tools/lsp_fake_pool: test plumbing only, no GPU)."""
+     tools/lsp_fake_pool: test plumbing only, no GPU).
+args: --inflight N adds column d and the ratios d_over_a, d_over_c."""
 import json
 import os
 import signal
@@ -34,9 +37,10 @@ MINER = os.path.join(ROOT, "p1_amd", "p1miner")
 LOAD = os.path.join(ROOT, "tools", "lsp_load")
 FAKE_MINER = os.path.join(ROOT, "tools", "lsp_fake_miner")
 FAKE_POOL = os.path.join(ROOT, "tools", "lsp_fake_pool")
+FAKE_POOL_ASYNC = os.path.join(ROOT, "tools", "lsp_fake_pool_async")
 
-SETUPS = [("a", "8 x p1miner lsp", 8, 0), ("b", "p1miner lsp --conns 8 --wide", 1, 8),
-          ("c", "p1miner lsp --conns 64 --wide", 1, 64)]
+SETUPS = [("a", "8 x p1miner lsp", 8, 0, 1), ("b", "p1miner lsp --conns 8 --wide", 1, 8, 1),
+          ("c", "p1miner lsp --conns 64 --wide", 1, 64, 1)]
 
 
 def load(hp, clients, jobs, prefix, max_nonce, errlog):
@@ -51,7 +55,7 @@ def load(hp, clients, jobs, prefix, max_nonce, errlog):
     return json.loads(r.stdout)
 
 
-def cell(size, nproc, conns, clients, jobs, fake, device):
+def cell(size, nproc, conns, clients, jobs, fake, device, inflight=1):
     procs = []
     errlog = tempfile.TemporaryFile(mode="w+")
     try:
@@ -64,8 +68,10 @@ def cell(size, nproc, conns, clients, jobs, fake, device):
         miners = []
         for _ in range(nproc):
             if conns:
-                argv = ([FAKE_POOL, hp] if fake else [MINER, "lsp", hp, "--device", device, "--wide"]) + \
-                    ["--conns", str(conns), "--stats"]
+                argv = ([FAKE_POOL_ASYNC if inflight > 1 else FAKE_POOL, hp] if fake else
+                        [MINER, "lsp", hp, "--device", device, "--wide"]) + ["--conns", str(conns), "--stats"]
+                if inflight > 1:
+                    argv += ["--inflight", str(inflight)]
             else:
                 argv = [FAKE_MINER, hp] if fake else [MINER, "lsp", hp, "--device", device]
             miners.append(subprocess.Popen(argv, stdout=subprocess.PIPE, stderr=errlog, text=True))
@@ -103,16 +109,26 @@ def main():
     fake = os.environ.get("FAKE") == "1"
     device = os.environ.get("DEVICE", "0")
     out = os.environ.get("OUT", os.path.join(ROOT, "profiles", "pool_bench.json"))
+    inflight = 1
+    if "--inflight" in sys.argv[1:]:
+        inflight = int(sys.argv[sys.argv.index("--inflight") + 1])
+    setups = list(SETUPS)
+    if inflight > 1:
+        setups.append(("d", f"p1miner lsp --conns 64 --wide --inflight {inflight}", 1, 64, inflight))
     rows, ok = [], True
     for size in sizes:
         row = {"nonces_per_job": size, "clients": clients, "jobs_per_client": jobs}
-        for key, what, nproc, conns in SETUPS:
-            row[key] = dict(cell(size, nproc, conns, clients, jobs, fake, device), setup=what)
+        for key, what, nproc, conns, depth in setups:
+            row[key] = dict(cell(size, nproc, conns, clients, jobs, fake, device, depth), setup=what)
             print(f"pool_bench: {size} nonces, {what}: {row[key]['jobs_per_s']:.0f} jobs/s, "
                   f"{row[key]['GH_s']:.2f} GH/s", file=sys.stderr, flush=True)
         row["checksums_agree"] = row["a"]["checksum"] == row["b"]["checksum"] == row["c"]["checksum"]
         row["b_over_a"] = row["b"]["jobs_per_s"] / row["a"]["jobs_per_s"]
         row["c_over_a"] = row["c"]["jobs_per_s"] / row["a"]["jobs_per_s"]
+        if "d" in row:
+            row["checksums_agree"] = row["checksums_agree"] and row["d"]["checksum"] == row["a"]["checksum"]
+            row["d_over_a"] = row["d"]["jobs_per_s"] / row["a"]["jobs_per_s"]
+            row["d_over_c"] = row["d"]["jobs_per_s"] / row["c"]["jobs_per_s"]
         ok = ok and row["checksums_agree"]
         rows.append(row)
     doc = {"workload": f"{clients} LSP clients x {jobs} jobs [0, size) each, messages job<client>-<job>, through "
