@@ -30,7 +30,8 @@ BUILD := build
 
 all: p1_amd/libp1hip.so oracle tools/p1emu tools/batch_emu p1_amd/p1miner p1_amd/p1server p1_amd/p1client tools/lsp_scenarios \
      tools/lsp_fake_miner tools/lsp_fake_pool tools/pool_test tools/async_slots_test tools/pool_pipeline_test \
-     tools/lsp_fake_pool_async tools/lsp_load tools/queue_ctl tools/wcal tools/vbank tools/libp1clock.so
+     tools/lsp_fake_pool_async p1_amd/p1gpuserver tools/lsp_fake_server_local tools/local_slots_test tools/lsp_jobs \
+     tools/lsp_load tools/queue_ctl tools/wcal tools/vbank tools/libp1clock.so
 
 # The assembly and object stages are intermediates: once the code object
 # exists, a tree without them (the GPU box's copy leaves the 16 MB of .s out,
@@ -85,7 +86,8 @@ p1_amd/libp1hip.so: $(BUILD)/p1hip_host.o $(BLOBS)
 # miner / server / client programs
 HOSTSRC := p1_amd/host/bitcoin.cpp p1_amd/host/lsp_message.cpp p1_amd/host/lsp.cpp p1_amd/host/lspnet.cpp
 HOSTHDR := p1_amd/host/bitcoin.hpp p1_amd/host/lsp_message.hpp p1_amd/host/gojson.hpp p1_amd/host/lsp.hpp \
-           p1_amd/host/lspnet.hpp p1_amd/host/scheduler.hpp p1_amd/host/miner_pool.hpp include/p1hip.h
+           p1_amd/host/lspnet.hpp p1_amd/host/scheduler.hpp p1_amd/host/miner_pool.hpp p1_amd/host/local_slots.hpp \
+           p1_amd/host/server_lsp.hpp include/p1hip.h
 HOSTFLAGS := -O2 -std=c++17 -Wall -Wextra -pthread
 
 p1_amd/p1miner: p1_amd/host/p1miner.cpp p1_amd/host/miner_gpu.cpp $(HOSTSRC) $(HOSTHDR) p1_amd/libp1hip.so
@@ -94,6 +96,11 @@ p1_amd/p1miner: p1_amd/host/p1miner.cpp p1_amd/host/miner_gpu.cpp $(HOSTSRC) $(H
 # the server schedules; its pipe-transport miners are p1miner processes
 p1_amd/p1server: p1_amd/host/p1server.cpp $(HOSTSRC) $(HOSTHDR)
 	g++ $(HOSTFLAGS) -o $@ p1_amd/host/p1server.cpp $(HOSTSRC)
+
+# the server that scans on its own GPU: p1server's LSP loop (server_lsp.hpp)
+# plus local slots (local_slots.hpp) over the pool's GPU backend
+p1_amd/p1gpuserver: p1_amd/host/p1gpuserver.cpp p1_amd/host/miner_gpu.cpp $(HOSTSRC) $(HOSTHDR) p1_amd/libp1hip.so
+	g++ $(HOSTFLAGS) -o $@ p1_amd/host/p1gpuserver.cpp p1_amd/host/miner_gpu.cpp $(HOSTSRC) -Lp1_amd -lp1hip -Wl,-rpath,'$$ORIGIN'
 
 # the client never touches the GPU (client.go): no libp1hip link
 p1_amd/p1client: p1_amd/host/p1client.cpp $(HOSTSRC) $(HOSTHDR)
@@ -128,6 +135,21 @@ tools/pool_pipeline_test: tests/pool_pipeline_test.cpp p1_amd/host/miner_pool.hp
 # CPU oracle (tests/test_pool_pipeline_host.py)
 tools/lsp_fake_pool_async: tests/lsp/lsp_fake_pool_async.cpp $(HOSTSRC) $(HOSTHDR) oracle
 	g++ $(HOSTFLAGS) -o $@ tests/lsp/lsp_fake_pool_async.cpp $(HOSTSRC) -Loracle -lp1oracle -Wl,-rpath,'$$ORIGIN/../oracle'
+
+# test double: p1gpuserver's loop and local slots over the CPU oracle on a
+# worker thread (tests/test_server_local_host.py)
+tools/lsp_fake_server_local: tests/lsp/lsp_fake_server_local.cpp $(HOSTSRC) $(HOSTHDR) oracle
+	g++ $(HOSTFLAGS) -o $@ tests/lsp/lsp_fake_server_local.cpp $(HOSTSRC) -Loracle -lp1oracle -Wl,-rpath,'$$ORIGIN/../oracle'
+
+# test client: one LSP connection, several Requests with any Lower / Upper
+# (tests/test_server_local_host.py, tests/test_gpu_server_local.py)
+tools/lsp_jobs: tests/lsp/lsp_jobs.cpp $(HOSTSRC) $(HOSTHDR)
+	g++ $(HOSTFLAGS) -o $@ tests/lsp/lsp_jobs.cpp $(HOSTSRC)
+
+# test program: server::LocalSlots over a Scheduler against the oracle's direct
+# scans, model-based (no LSP; tests/test_local_slots_host.py)
+tools/local_slots_test: tests/local_slots_test.cpp $(HOSTHDR) oracle
+	g++ $(HOSTFLAGS) -o $@ tests/local_slots_test.cpp -Loracle -lp1oracle -Wl,-rpath,'$$ORIGIN/../oracle'
 
 # measurement program: many LSP clients in one process (tools/pool_bench.py)
 tools/lsp_load: tools/lsp_load.cpp $(HOSTSRC) $(HOSTHDR)
@@ -182,7 +204,7 @@ SAN_asan := -fsanitize=address,undefined -fno-sanitize-recover=undefined
 SAN_tsan := -fsanitize=thread
 SANDIR := $(BUILD)/san
 SANPROGS := lsp_scenarios sched_test p1server p1client lsp_fake_miner lsp_fake_pool pool_test \
-            async_slots_test pool_pipeline_test lsp_fake_pool_async
+            async_slots_test pool_pipeline_test lsp_fake_pool_async local_slots_test lsp_fake_server_local
 sanitize: $(foreach s,asan tsan,$(addprefix $(SANDIR)/$(s)/,$(SANPROGS)))
 sanitize-emu: $(SANDIR)/asan/p1emu $(SANDIR)/asan/batch_emu
 
@@ -216,6 +238,12 @@ $(SANDIR)/%/pool_pipeline_test: tests/pool_pipeline_test.cpp p1_amd/host/miner_p
 $(SANDIR)/%/lsp_fake_pool_async: tests/lsp/lsp_fake_pool_async.cpp $(HOSTSRC) $(HOSTHDR) oracle
 	mkdir -p $(@D)
 	$(SANCXX) $(SANBASE) $(SAN_$*) -o $@ tests/lsp/lsp_fake_pool_async.cpp $(HOSTSRC) -L$(CURDIR)/oracle -lp1oracle -Wl,-rpath,$(CURDIR)/oracle
+$(SANDIR)/%/local_slots_test: tests/local_slots_test.cpp $(HOSTHDR) oracle
+	mkdir -p $(@D)
+	$(SANCXX) $(SANBASE) $(SAN_$*) -o $@ tests/local_slots_test.cpp -L$(CURDIR)/oracle -lp1oracle -Wl,-rpath,$(CURDIR)/oracle
+$(SANDIR)/%/lsp_fake_server_local: tests/lsp/lsp_fake_server_local.cpp $(HOSTSRC) $(HOSTHDR) oracle
+	mkdir -p $(@D)
+	$(SANCXX) $(SANBASE) $(SAN_$*) -o $@ tests/lsp/lsp_fake_server_local.cpp $(HOSTSRC) -L$(CURDIR)/oracle -lp1oracle -Wl,-rpath,$(CURDIR)/oracle
 # the library's host runtime under ASan + UBSan (host side only: the kernels
 # are the shipped code object) and its GPU stress driver; in tools/san, not
 # build/, so that they travel to the GPU box with the tree
@@ -294,7 +322,8 @@ isa: $(BUILD)/p1hip_kernels.post.s
 
 clean:
 	rm -f p1_amd/libp1hip.so tools/libp1clock.so tools/queue_ctl tools/p1emu tools/batch_emu p1_amd/p1miner p1_amd/p1server p1_amd/p1client tools/lsp_scenarios tools/lsp_fake_miner tools/lsp_fake_pool tools/pool_test tools/lsp_load tools/wcal tools/vbank \
-	    tools/async_slots_test tools/pool_pipeline_test tools/lsp_fake_pool_async
+	    tools/async_slots_test tools/pool_pipeline_test tools/lsp_fake_pool_async p1_amd/p1gpuserver tools/lsp_fake_server_local \
+    tools/local_slots_test tools/lsp_jobs
 	rm -rf $(BUILD)/p1hip_kernels* $(BUILD)/p1hip_batch* $(BUILD)/p1hip_host.o
 	$(MAKE) -C oracle clean
 .PHONY: all oracle clean isa variant sanitize sanitize-emu sanitize-lib sanitize-lib-tsan fuzz

@@ -12,6 +12,7 @@ ARTEFACTS = ["p1_amd/libp1hip.so", "oracle/libp1oracle.so", "p1_amd/p1miner", "p
              "tools/p1emu", "tools/batch_emu",
              "tools/lsp_scenarios", "tools/lsp_fake_miner", "tools/lsp_fake_pool", "tools/pool_test",
              "tools/async_slots_test", "tools/pool_pipeline_test", "tools/lsp_fake_pool_async",
+             "p1_amd/p1gpuserver", "tools/lsp_fake_server_local", "tools/local_slots_test", "tools/lsp_jobs",
              "tools/libp1clock.so"]
 
 

@@ -12,6 +12,11 @@
 //       encoding/json bitcoin.Message in an LSP payload.  A lost miner's chunk
 //       is re-queued, a lost client's request dropped.  --exit-after N: exit 0
 //       after answering N requests (tests, benchmarks); otherwise runs forever.
+//       The loop is server_lsp.hpp's, which p1gpuserver shares: that program
+//       is this server plus local slots that scan on the server's own GPU
+//       (local_slots.hpp).  This one links neither libp1hip nor the oracle, so
+//       a box without ROCm still starts it; it takes none of p1gpuserver's
+//       flags.
 //   p1server [opts] scan <msg> <lower> <upper>    one request over child-process
 //       miners ("p1miner serve" on pipes); prints "Result <hash> <nonce>"
 //   p1server [opts] serve                         JSON Requests on stdin -> JSON
@@ -44,56 +49,9 @@
 #include "lsp.hpp"
 #include "lspnet.hpp"
 #include "scheduler.hpp"
+#include "server_lsp.hpp"
 
 namespace {
-
-// ----------------------------------------------------------------------------
-// LSP transport (server.go:83-168)
-// ----------------------------------------------------------------------------
-int run_lsp(int port, const lsp::Params& prm, uint64_t chunk, long exit_after) {
-  std::string err;
-  std::unique_ptr<lsp::Server> srv = lsp::NewServer(port, prm, &err);
-  if (!srv) {
-    printf("%s\n", err.c_str());
-    return 1;
-  }
-  printf("Server listening on port %d\n", srv->Port());
-  fflush(stdout);
-  sched::Scheduler S(chunk);
-  long answered = 0;
-  for (;;) {
-    int id = 0;
-    std::string payload;
-    if (!srv->Read(&id, &payload, &err)) {
-      if (id == 0) return 1;  // server closed
-      // a lost connection: a miner's chunk is re-queued, a client's request dropped
-      if (S.IsMiner(id)) S.LoseMiner(id);
-      else S.CancelClient(id);
-    } else {
-      // server.go:117 ignores Unmarshal's error and switches on whatever was
-      // decoded: a type error (say a negative Lower) still yields the rest of
-      // the message.  Unlike the reference, a payload that is not JSON at all
-      // is dropped rather than read as a zero Message (a Join).
-      bitcoin::Message m;
-      if (bitcoin::UnmarshalStatus(payload, &m) != gojson::kSyntaxError) {
-        switch (m.Type) {
-          case bitcoin::Join: S.AddMiner(id); break;
-          case bitcoin::Request: S.Submit(id, m.Data, m.Lower, m.Upper); break;
-          case bitcoin::Result: S.Result(id, m.Hash, m.Nonce); break;
-        }
-      }
-    }
-    for (const sched::Assignment& a : S.Dispatch())
-      if (!srv->Write(a.miner, bitcoin::Marshal(bitcoin::NewRequest(a.data, a.lo, a.hi)))) S.Unassign(a.miner);
-    for (const sched::Done& d : S.TakeDone()) {
-      srv->Write((int)d.client, bitcoin::Marshal(bitcoin::NewResult(d.hash, d.nonce)));  // client may be gone
-      if (exit_after > 0 && ++answered >= exit_after) {
-        srv->Close();  // blocks until the results are acknowledged
-        return 0;
-      }
-    }
-  }
-}
 
 // ----------------------------------------------------------------------------
 // Child-process transport: each miner is "p1miner serve" on a pipe pair,
@@ -300,7 +258,7 @@ int main(int argc, char** argv) {
       printf("Port must be a number: %s\n", argv[i + 1]);  // server.go:68-72
       return 1;
     }
-    return run_lsp((int)port, prm, chunk, exit_after);
+    return server::RunLsp((int)port, prm, chunk, exit_after);  // server_lsp.hpp
   }
   if (mode != "scan" && mode != "serve") return usage();
   PipeServer srv(nminers, devs, chunk, cmd);

@@ -84,7 +84,13 @@ class Scheduler {
     }
   }
 
-  void AddMiner(int miner) { miners_[miner]; }  // idle (server.go:153-166)
+  // A Join: the miner is idle (server.go:153-166).  `chunk` (0: the
+  // scheduler's own) bounds the chunks carved for this miner; the server's
+  // local slots (local_slots.hpp) ask for smaller ones than remote miners
+  // get.  A chunk handed back by a lost miner keeps its own bounds when it is
+  // re-dealt (Req::take), so it may be larger than its next taker's chunk:
+  // that is accepted, a taker chunks nothing itself and scans what it is given.
+  void AddMiner(int miner, uint64_t chunk = 0) { miners_[miner].chunk = chunk; }
   bool IsMiner(int miner) const { return miners_.count(miner) != 0; }
   size_t Miners() const { return miners_.size(); }
 
@@ -143,7 +149,7 @@ class Scheduler {
         auto it = reqs_.find(id);
         if (it == reqs_.end() || !it->second.has_work()) continue;
         Req& r = it->second;
-        const Span c = r.take(chunk_);
+        const Span c = r.take(m.chunk ? m.chunk : chunk_);
         r.inflight[c.lo] = {c.hi};
         assign(kv.first, m, r, c.lo, c.hi, out);
         any = true;
@@ -224,6 +230,7 @@ class Scheduler {
     }
   };
   struct Miner {
+    uint64_t chunk = 0;  // nonces per chunk carved for it; 0: chunk_
     bool busy = false;
     uint64_t cur_req = 0, lo = 0, hi = 0;
   };

@@ -4,8 +4,8 @@
 #   tools/sanitize.sh [out.json]
 #
 # Builds `make sanitize` (ASan+UBSan and TSan builds of the LSP stack, the
-# server, the client, the CPU test-double miner and pool, and the scheduler
-# and pool unit tests)
+# server, the client, the CPU test-double miner and pool, the self-scanning
+# server's double and the scheduler, pool and local-slots unit tests)
 # and, when present, build/san/asan/p1emu and build/san/asan/batch_emu
 # (`make sanitize-emu`, ~6 min: the planner + every kernel variant, and a
 # p1hip_scan_batch call, replayed on the host).  Then re-runs the
@@ -25,7 +25,9 @@ for san in asan tsan; do
   export ASAN_OPTIONS="detect_leaks=1:log_path=$logs/asan"
   export UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1:log_path=$logs/ubsan"
   export TSAN_OPTIONS="halt_on_error=0:log_path=$logs/tsan"
-  tests="tests/test_lsp.py tests/test_lsp_bitcoin.py tests/test_server.py tests/test_pool_host.py"
+  # test_server_local_host.py and test_local_slots_host.py start the stand-alone
+  # programs lsp_fake_server_local and local_slots_test of this build directly
+  tests="tests/test_lsp.py tests/test_lsp_bitcoin.py tests/test_server.py tests/test_pool_host.py tests/test_server_local_host.py tests/test_local_slots_host.py"
   if [ "$san" = asan ] && [ -x build/san/asan/p1emu ]; then
     tests="$tests tests/test_host_logic.py"
   fi
