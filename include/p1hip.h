@@ -298,6 +298,67 @@ typedef struct {
 } p1hip_async_stats_t;
 int p1hip_get_async_stats(p1hip_async_stats_t *out);   /* cleared by p1hip_reset_stats */
 
+/* Every nonce whose hash is at or below a target.  The calls above answer
+ * "the minimum over a range"; a miner is normally asked the other question:
+ *     for i := lower; i <= upper; i++ { if bitcoin.Hash(data, i) <= target { hits = append(hits, i) } }
+ * With cap == 1 that is "the first nonce that meets the target", with a larger
+ * cap "every share in the range".
+ *
+ * hits = the nonces n of [lower, upper] (inclusive) with bitcoin.Hash(msg, n)
+ * <= target, in increasing n, the first `cap` of them; hits[i] = {hash, nonce}.
+ * *found < cap: these are ALL hits of the range.  *found == cap: there may be
+ * more; resume with lower = hits[cap-1].nonce + 1.
+ * The comparison is <=: target 0 asks for a hash equal to 0, UINT64_MAX for
+ * every nonce.  lower > upper or cap == 0 gives *found = 0 with rc 0 and opens
+ * no device.  upper == UINT64_MAX is scanned inclusively.  Arguments are
+ * validated as p1hip_scan validates them; `hits` and `found` are written only
+ * on success.  Synchronous, serialised under the library's lock, lazy init as
+ * in p1hip_scan; legal while tickets are outstanding (it owns every buffer it
+ * adds, and shares p1hip_scan's otherwise).  The result is defined by the loop
+ * above alone: slicing, route and device count never show in it.
+ *
+ * The range is scanned in consecutive slices and the call returns after the
+ * first slice that brings the total to `cap`.  A slice is twice the nonces
+ * expected to hold the missing hits, 2 * want * 2^64 / (target + 1), rounded
+ * up to a power of two and clamped to [2^16, P1HIP_BELOW_MAX_SLICE].  A slice
+ * takes one of two routes, chosen from the target:
+ *   sparse (target < P1HIP_BELOW_DENSE_TARGET): the slice is scanned exactly
+ *     as p1hip_scan scans it (same plan, tables, packing, devices); k_scan's
+ *     16-byte partial per tile, the tile's minimum, is the filter: only tiles
+ *     whose partial is at or below the target are looked at nonce by nonce, by
+ *     k_below_mark (one bit per nonce) on the first device.
+ *   dense (otherwise, at most P1HIP_BELOW_MAX_SLICE_DENSE nonces a slice; and
+ *     any slice of at most 2^16 nonces): every nonce goes straight to
+ *     k_below_mark.
+ * Two checks stay in the product, a failure of either is P1HIP_ERR_HIP: every
+ * marked nonce's hash, recomputed on the host, is at or below the target; and
+ * the marks of every refined tile have exactly the tile's partial (hash,
+ * nonce) as their lexicographic minimum. */
+#define P1HIP_BELOW_MAX_SLICE ((uint64_t)1 << 34)
+#define P1HIP_BELOW_MAX_SLICE_DENSE ((uint64_t)1 << 28)
+#define P1HIP_BELOW_DENSE_TARGET ((uint64_t)1 << 46)
+int p1hip_scan_below(const uint8_t *msg, size_t msg_len, uint64_t lower, uint64_t upper,
+                     uint64_t target, size_t cap, p1hip_result_t *hits, size_t *found);
+
+/* Accounting of p1hip_scan_below since p1hip_reset_stats.  Its k_scan launches
+ * also count in the p1hip_device_stats_t of the device that ran them, as
+ * scan_launches, scan_nonces, scan_alg_ops and scan_kernel_ms; nothing of it
+ * counts in p1hip_stats_t. */
+typedef struct {
+  uint64_t calls;            /* p1hip_scan_below calls that succeeded             */
+  uint64_t slices;           /* slices they ran                                   */
+  uint64_t sparse_slices;    /* ... filtered by k_scan                            */
+  uint64_t dense_slices;     /* ... marked nonce by nonce                         */
+  uint64_t examined;         /* nonces of the finished slices                     */
+  uint64_t scan_nonces;      /* nonces hashed by k_scan (sparse slices)           */
+  uint64_t mark_nonces;      /* nonces hashed by k_below_mark                     */
+  uint64_t candidate_tiles;  /* k_scan tiles whose partial was <= target          */
+  uint64_t mark_launches;    /* k_below_mark launches                             */
+  uint64_t hits;             /* hits returned                                     */
+  double wall_ms;            /* host wall time inside p1hip_scan_below            */
+} p1hip_below_stats_t;
+int p1hip_get_below_stats(p1hip_below_stats_t *out);   /* cleared by p1hip_reset_stats */
+
 /* Kernel-level accounting.  One p1hip_scan = one (rarely several) launch of
  * the scan kernel k_scan per device, covering every decade of the range; a
  * share of at most 2^16 nonces is one launch of k_scan_small instead (plan in
@@ -388,8 +449,9 @@ int p1hip_comm_info(int index, int *nranks, int *rank);
  * p1hip_get_wide_stats and p1hip_wide_stats_t, and with the test hook
  * p1hip_scan_tiles and its p1hip_tile_t, and with p1hip_batch_submit,
  * p1hip_batch_wait, p1hip_get_async_stats, p1hip_async_stats_t and
- * P1HIP_ERR_BUSY: purely additive, the layout of every existing struct is
- * unchanged. */
+ * P1HIP_ERR_BUSY, and with p1hip_scan_below, p1hip_get_below_stats,
+ * p1hip_below_stats_t and the P1HIP_BELOW_* constants: purely additive, the
+ * layout of every existing struct is unchanged. */
 #define P1HIP_ABI_VERSION 6
 int p1hip_abi_version(void);
 

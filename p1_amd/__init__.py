@@ -46,5 +46,11 @@ from ._lib import (  # noqa: F401
     codeobj_bytes,
     codeobj_sha256,
     batch_codeobj_sha256,
+    scan_below,
+    get_below_stats,
+    below_codeobj_sha256,
+    BELOW_MAX_SLICE,
+    BELOW_MAX_SLICE_DENSE,
+    BELOW_DENSE_TARGET,
 )
 from .sharding import shard_range, combine_keys  # noqa: F401

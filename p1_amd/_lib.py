@@ -123,6 +123,25 @@ class AsyncStats(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class BelowStats(ctypes.Structure):
+    _fields_ = [
+        ("calls", U64),
+        ("slices", U64),
+        ("sparse_slices", U64),
+        ("dense_slices", U64),
+        ("examined", U64),
+        ("scan_nonces", U64),
+        ("mark_nonces", U64),
+        ("candidate_tiles", U64),
+        ("mark_launches", U64),
+        ("hits", U64),
+        ("wall_ms", ctypes.c_double),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class DeviceInfo(ctypes.Structure):
     _fields_ = [
         ("ordinal", ctypes.c_int32),
@@ -189,6 +208,10 @@ SIGNATURES = [
      [ctypes.POINTER(Request), ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(U64)]),
     ("p1hip_batch_wait", ctypes.c_int, [U64, ctypes.POINTER(Result)]),
     ("p1hip_get_async_stats", ctypes.c_int, [ctypes.POINTER(AsyncStats)]),
+    ("p1hip_scan_below", ctypes.c_int,
+     [ctypes.c_char_p, ctypes.c_size_t, U64, U64, U64, ctypes.c_size_t, ctypes.POINTER(Result),
+      ctypes.POINTER(ctypes.c_size_t)]),
+    ("p1hip_get_below_stats", ctypes.c_int, [ctypes.POINTER(BelowStats)]),
     ("p1hip_hash", ctypes.c_int, [ctypes.c_char_p, ctypes.c_size_t, U64, ctypes.POINTER(U64)]),
     ("p1hip_plan_shards", ctypes.c_int,
      [ctypes.c_char_p, ctypes.c_size_t, U64, U64, ctypes.c_int, ctypes.POINTER(U64), ctypes.POINTER(U64)]),
@@ -383,6 +406,45 @@ def get_async_stats():
     s = AsyncStats()
     _check(load().p1hip_get_async_stats(ctypes.byref(s)))
     return s.as_dict()
+
+
+# include/p1hip.h P1HIP_BELOW_MAX_SLICE, P1HIP_BELOW_MAX_SLICE_DENSE, P1HIP_BELOW_DENSE_TARGET
+BELOW_MAX_SLICE = 1 << 34
+BELOW_MAX_SLICE_DENSE = 1 << 28
+BELOW_DENSE_TARGET = 1 << 46
+
+
+def scan_below(msg, lower, upper, target, cap=1):
+    """p1hip_scan_below: [(hash, nonce)] of the nonces n of [lower, upper] with
+    bitcoin.Hash(msg, n) <= target, in increasing n, the first `cap` of them.
+    Fewer than `cap`: these are all hits of the range; exactly `cap`: there
+    may be more, resume with lower = the last nonce + 1."""
+    m = _bytes(msg)
+    cap = int(cap)
+    out = (Result * max(cap, 1))()
+    found = ctypes.c_size_t(0)
+    _check(load().p1hip_scan_below(m, len(m), int(lower), int(upper), int(target), cap, out, ctypes.byref(found)))
+    return [(out[i].hash, out[i].nonce) for i in range(found.value)]
+
+
+def get_below_stats():
+    """Accounting of scan_below since reset_stats (p1hip_get_below_stats)."""
+    s = BelowStats()
+    _check(load().p1hip_get_below_stats(ctypes.byref(s)))
+    return s.as_dict()
+
+
+def below_codeobj_sha256(lib=None):
+    """sha256 (hex) of the third embedded code object, the mark kernel of
+    scan_below (p1hip_below_co .. p1hip_below_co_end of csrc/p1hip_below_blob.S)."""
+    import hashlib
+
+    lib = lib or load()
+    start = ctypes.addressof(ctypes.c_char.in_dll(lib, "p1hip_below_co"))
+    end = ctypes.addressof(ctypes.c_char.in_dll(lib, "p1hip_below_co_end"))
+    if end <= start:
+        raise P1HipError(-100, "embedded below code object is empty")
+    return hashlib.sha256(ctypes.string_at(start, end - start)).hexdigest()
 
 
 def batch_codeobj_sha256(lib=None):

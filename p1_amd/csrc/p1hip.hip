@@ -34,8 +34,17 @@
 // event per device; wait blocks on the events with the runtime mutex released.
 // Still one stream per device: k_scan's work-queue ticket is shared.
 //
+// p1hip_scan_below: every nonce whose hash is at or below a target, slice by
+// slice.  A sparse slice runs the scan path's own run_range on every device
+// and keeps the tiles whose partial is at or below the target; k_below_mark
+// (a third code object, p1hip_below_kernels.hip, p1hip_below_blob.S) answers
+// one bit per nonce of those tiles, or of the whole slice when it is dense.
+// Slices, filter, tables and decoder come from below_plan.hpp, which
+// tools/p1emu shares.
+//
 // Order of this file: runtime state, helpers, the scan path, the batch path,
-// the wide path, submit / wait, reduce_pairs, scan_tiles, then the C ABI in one extern "C" block.  Every HIP and RCCL
+// the wide path, submit / wait, reduce_pairs, scan_tiles, scan_below, then the
+// C ABI in one extern "C" block.  Every HIP and RCCL
 // call of the library is in this file (tests/test_stream_discipline.py).
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -57,15 +66,18 @@
 #include "../../include/p1hip.h"
 #include "async_slots.hpp"
 #include "batch_plan.hpp"
+#include "below_plan.hpp"
 #include "planner.hpp"
 #include "scan_abi.hpp"
 #include "scan_pack.hpp"
 #include "tile_map.hpp"
 #include "wide_plan.hpp"
 
-// the embedded gfx950 code objects (p1hip_kernels_blob.S, p1hip_batch_blob.S)
+// the embedded gfx950 code objects (p1hip_kernels_blob.S, p1hip_batch_blob.S,
+// p1hip_below_blob.S)
 extern "C" const unsigned char p1hip_kernels_co[];
 extern "C" const unsigned char p1hip_batch_co[];
+extern "C" const unsigned char p1hip_below_co[];
 
 using namespace p1;
 
@@ -132,7 +144,8 @@ enum KnobWhen { kPerScan, kPerBatch, kAtInit };  // init: the open devices keep 
 enum KnobId {
   kSmallMaxNoncesKnob, kMaxLaunchBlocksKnob, kMaxScanSpanKnob, kKwtabMaxBytesKnob, kNoRcclKnob, kForceRcclKnob,
   kMinFastThreadsKnob, kTestFailDeviceKnob, kNoTableKnob, kNoSplitKnob, kScanGridKnob, kBatchMaxNoncesKnob,
-  kBatchMaxTilesKnob, kWideMaxNoncesKnob, kWideMaxSegsKnob, kWideMinFastThreadsKnob, kKnobCount
+  kBatchMaxTilesKnob, kWideMaxNoncesKnob, kWideMaxSegsKnob, kWideMinFastThreadsKnob, kBelowPathKnob,
+  kBelowMaxSliceKnob, kKnobCount
 };
 struct Knob {
   const char* name;
@@ -182,6 +195,12 @@ const Knob kKnobs[] = {
     {"P1HIP_WIDE_MIN_FAST_THREADS", 0, ~0ull, kZeroDef, kPerBatch,
      "occupancy floor the wide requests are planned with instead of wide_min_fast_threads' rule (the default, "
      "0); 1 keeps k = 3"},
+    {"P1HIP_BELOW_PATH", kBelowAuto, kBelowDense, kValue, kPerScan,
+     "route of every slice of p1hip_scan_below: 0 chosen from the target (the default), 1 sparse (k_scan filters, "
+     "the surviving tiles are marked), 2 dense (every nonce is marked), so GPU tests run both on one range"},
+    {"P1HIP_BELOW_MAX_SLICE", 0, ~0ull, kZeroDef, kPerScan,
+     "nonces per slice of p1hip_scan_below at the most, below the route's own limit, so GPU tests run several "
+     "slices, with hits next to their edges, on small ranges"},
 };
 static_assert(sizeof kKnobs / sizeof kKnobs[0] == kKnobCount, "one row per KnobId, in its order");
 
@@ -321,6 +340,14 @@ struct Dev {
   // and the ticket with p1hip_scan, d_bseg, d_btile0 and d_bout with the batch)
   DevBuf<WideRange> d_wrange;
   PinnedBuf<WideRange> h_wrange;
+  // p1hip_scan_below: its own code object and buffers (the table and the
+  // marks of one k_below_mark launch; its sparse slices run in p1hip_scan's)
+  hipModule_t lmod = nullptr;
+  hipFunction_t f_mark = nullptr;
+  DevBuf<BatchSeg> d_mseg;
+  PinnedBuf<BatchSeg> h_mseg;
+  DevBuf<uint64_t> d_marks;     // kBelowWordsPerTile words per tile
+  PinnedBuf<uint64_t> h_marks;
   SlotDev slot[P1HIP_MAX_INFLIGHT];  // p1hip_batch_submit: one buffer set per ticket slot
   std::vector<hipEvent_t> evs;  // profiling event pool (pairs)
   // MODE 5 K+W tables on this device, least recently used first (built by
@@ -385,6 +412,7 @@ struct Runtime {
   p1hip_stats_t stats{};
   p1hip_batch_stats_t bstats{};
   p1hip_wide_stats_t wstats{};
+  p1hip_below_stats_t lstats{};
 };
 
 // Never destroyed: the runtime state outlives every static destructor, so a
@@ -480,6 +508,7 @@ int dev_release(Dev& d) {
   if (d.stream) (void)hipStreamDestroy(d.stream);
   if (d.mod) (void)hipModuleUnload(d.mod);
   if (d.bmod) (void)hipModuleUnload(d.bmod);
+  if (d.lmod) (void)hipModuleUnload(d.lmod);
   d = Dev();  // every Buf frees itself here: this device is current, its work is done
   return 0;
 }
@@ -534,6 +563,8 @@ int init_devs(Runtime& R, const std::vector<int>& ords) {
     HIPCHK(hipModuleGetFunction(&d.f_bscan, d.bmod, "k_batch_scan"));
     HIPCHK(hipModuleGetFunction(&d.f_breduce, d.bmod, "k_batch_reduce"));
     HIPCHK(hipModuleGetFunction(&d.f_wreduce, d.bmod, "k_wide_reduce"));
+    HIPCHK(hipModuleLoadData(&d.lmod, p1hip_below_co));
+    HIPCHK(hipModuleGetFunction(&d.f_mark, d.lmod, "k_below_mark"));
     // fixed-size buffers: floor = need, so exactly that many elements
     HIPCHK(d.d_small_part.reserve(kSmallMaxBlocks, kSmallMaxBlocks));
     HIPCHK(d.d_ticket.reserve(1, 1));
@@ -601,6 +632,9 @@ int ensure_init(Runtime& R) {
 // first launch, and after the last they wait for the stream and copy the raw
 // partials and the result back, next to the tile map of the plan they ran.
 // The product path passes none: nothing is poisoned or copied there.
+// p1hip_scan_below's sparse slices take the same map and partials as their
+// filter: run_range without the poison (every partial of the scan is written)
+// and without the collect, which follows once every device is enqueued.
 struct TileDump {
   std::vector<TileInfo> map;
   std::vector<Key> part;
@@ -722,8 +756,11 @@ uint32_t scan_grid_for(const Dev& d, uint32_t tiles) {
 }
 
 // Run one device's share [lo, hi] (lo <= hi) and leave its Key in d.d_res.
+// With a `dump`: its map is filled in; `poison` fills the partials first and
+// `collect` ends with dump_collect (else the caller collects).
 int run_range(Dev& d, const uint8_t* msg, size_t len, uint64_t lo, uint64_t hi, bool profiling,
-              uint64_t min_fast_threads, bool split, bool tabulate, TileDump* dump = nullptr) {
+              uint64_t min_fast_threads, bool split, bool tabulate, TileDump* dump = nullptr, bool poison = true,
+              bool collect = true) {
   HIPCHK(hipSetDevice(d.ordinal));
   d.range_id++;  // tables referenced from here on are pinned until the next call
   d.ctr = {};
@@ -758,7 +795,7 @@ int run_range(Dev& d, const uint8_t* msg, size_t len, uint64_t lo, uint64_t hi, 
   int rc;
   if (dump) {
     dump->map = tile_map(plan, P);
-    if ((rc = dump_poison(d, d.d_part.p, P.total_blocks))) return rc;
+    if (poison && (rc = dump_poison(d, d.d_part.p, P.total_blocks))) return rc;
   }
   size_t nev = 0;
   uint32_t part_off = 0;
@@ -783,7 +820,7 @@ int run_range(Dev& d, const uint8_t* msg, size_t len, uint64_t lo, uint64_t hi, 
   }
   HIPCHK(launch(d.f_reduce, 1, kReduceThreads, d.stream, (const Key*)d.d_part.p, P.total_blocks, d.d_res.p));
   if ((rc = ev_sum(d, nev))) return rc;
-  return dump ? dump_collect(d, d.d_part.p, *dump) : P1HIP_OK;
+  return dump && collect ? dump_collect(d, d.d_part.p, *dump) : P1HIP_OK;
 }
 
 // A device's share, in pieces of at most kMaxScanSpan nonces: the plan of a
@@ -1653,6 +1690,152 @@ int scan_tiles_locked(const uint8_t* msg, size_t msg_len, uint64_t lower, uint64
   return P1HIP_OK;
 }
 
+// ----------------------------------------------------------------------------
+// p1hip_scan_below
+// ----------------------------------------------------------------------------
+// the public header restates below_abi.hpp's constants
+static_assert(P1HIP_BELOW_MAX_SLICE == kBelowMaxSliceSparse && P1HIP_BELOW_MAX_SLICE_DENSE == kBelowMaxSliceDense &&
+                  P1HIP_BELOW_DENSE_TARGET == kBelowDenseTarget,
+              "p1hip.h and below_abi.hpp disagree");
+
+// One launch of k_below_mark on device d: table B up, the kernel, the marks
+// back into d.h_marks; synchronises.  Workgroup b of the B.tiles launched
+// writes words [4b, 4b + 4) of the 4 * B.tiles reserved, every one of them, so
+// the marks are not cleared first.  The buffers are this path's own and grow
+// only here, between two synchronised launches of it.
+int below_mark(Dev& d, const BelowTable& B, uint64_t target) {
+  const size_t nseg = B.T.segs.size(), words = (size_t)B.tiles * kBelowWordsPerTile;
+  HIPCHK(hipSetDevice(d.ordinal));
+  HIPCHK(d.d_mseg.reserve(nseg, 64));
+  HIPCHK(d.h_mseg.reserve(nseg, 64));
+  HIPCHK(d.d_marks.reserve(words, 4096));
+  HIPCHK(d.h_marks.reserve(words, 4096));
+  memcpy(d.h_mseg.p, B.T.segs.data(), nseg * sizeof(BatchSeg));
+  HIPCHK(hipMemcpyAsync(d.d_mseg.p, d.h_mseg.p, nseg * sizeof(BatchSeg), hipMemcpyHostToDevice, d.stream));
+  HIPCHK(launch(d.f_mark, B.tiles, kBlock, d.stream, (const BatchSeg*)d.d_mseg.p, (uint32_t)nseg, target, d.d_marks.p));
+  HIPCHK(hipMemcpyAsync(d.h_marks.p, d.d_marks.p, words * sizeof(uint64_t), hipMemcpyDeviceToHost, d.stream));
+  HIPCHK(hipStreamSynchronize(d.stream));
+  return P1HIP_OK;
+}
+
+// Pass 1 of a sparse slice: [lo, hi] cut across the open devices as p1hip_scan
+// cuts it, run_range on each with p1hip_scan's settings -- every device
+// enqueued before any is synchronised -- and the tiles whose partial is at or
+// below the target turned into pieces (below_plan.hpp).  No combine: the
+// partials are all the filter needs.
+int below_filter(Runtime& R, const uint8_t* msg, size_t msg_len, uint64_t lo, uint64_t hi, uint64_t target,
+                 std::vector<BelowPiece>& pieces, std::vector<Key>& cand_part, p1hip_below_stats_t& add) {
+  const size_t nd = R.devs.size();
+  std::vector<uint64_t> slo(nd), shi(nd);
+  plan_shards(msg, msg_len, lo, hi, (int)nd, slo.data(), shi.data());
+  std::vector<TileDump> dumps(nd);
+  int rc;
+  for (size_t i = 0; i < nd; ++i) {
+    if (slo[i] > shi[i]) continue;
+    Dev& d = R.devs[i];
+    d.replans = 0;
+    if ((rc = run_range(d, msg, msg_len, slo[i], shi[i], R.profiling, R.min_fast_threads, R.split, R.tabulate,
+                        &dumps[i], false, false)))
+      return rc;
+    add.scan_nonces += d.ctr.scan_nonces;
+    d.acc.scan_launches += d.ctr.scan_launches;
+    d.acc.scan_nonces += d.ctr.scan_nonces;
+    d.acc.scan_alg_ops += d.ctr.scan_ops;
+    d.acc.scan_kernel_ms += d.ctr.scan_ms;
+  }
+  for (size_t i = 0; i < nd; ++i) {
+    if (slo[i] > shi[i]) continue;
+    Dev& d = R.devs[i];
+    HIPCHK(hipSetDevice(d.ordinal));
+    if ((rc = dump_collect(d, d.d_part.p, dumps[i]))) return rc;
+    for (size_t t = 0; t < dumps[i].map.size(); ++t)
+      if (below_candidate(dumps[i].map[t], dumps[i].part[t], target)) {
+        below_tile_pieces(dumps[i].map[t], (uint32_t)cand_part.size(), pieces);
+        cand_part.push_back(dumps[i].part[t]);
+      }
+  }
+  return P1HIP_OK;
+}
+
+int scan_below_locked(const uint8_t* msg, size_t msg_len, uint64_t lower, uint64_t upper, uint64_t target, size_t cap,
+                      p1hip_result_t* hits, size_t* found) {
+  Runtime& R = rt();
+  std::lock_guard<std::mutex> g(R.mu);
+  const auto t0 = std::chrono::steady_clock::now();
+  int rc = ensure_init(R);
+  if (rc) return rc;
+  const int path = (int)knob(kBelowPathKnob);
+  const uint64_t max_slice = knob(kBelowMaxSliceKnob);
+  // results are gathered here and copied to `hits` only when the whole call has succeeded
+  std::vector<p1hip_result_t> res;
+  p1hip_below_stats_t add{};
+  auto run = [&]() -> int {
+    std::vector<BelowPiece> pieces;
+    std::vector<Key> cand_part;
+    std::vector<BelowHit> got;
+    BelowTable B;
+    for (uint64_t lo = lower;;) {
+      const size_t want = cap - res.size();
+      const BelowSlice S = below_next_slice(lo, upper, target, want, path, max_slice);
+      pieces.clear();
+      cand_part.clear();
+      got.clear();
+      if (S.dense) {
+        below_dense_pieces(S.lo, S.hi, pieces);
+        add.dense_slices++;
+      } else {
+        if ((rc = below_filter(R, msg, msg_len, S.lo, S.hi, target, pieces, cand_part, add))) return rc;
+        add.sparse_slices++;
+        add.candidate_tiles += cand_part.size();
+      }
+      // the mark launches, on the first device; a dense slice's pieces are in
+      // nonce order, so it may stop at the hits still wanted
+      for (size_t first = 0; first < pieces.size() && got.size() < (S.dense ? want : ~(size_t)0); first += B.count) {
+        std::string err = below_build_table(msg, msg_len, pieces, first, B);
+        if (!err.empty()) return fail(P1HIP_ERR_ARGS, err);
+        if (B.count == 0 || B.tiles == 0) return fail(P1HIP_ERR_HIP, "internal: empty refine table");
+        if ((rc = below_mark(R.devs[0], B, target))) return rc;
+        add.mark_launches++;
+        add.mark_nonces += B.T.nonces;
+        err = below_decode(B, pieces, R.devs[0].h_marks.p, target, S.dense ? want - got.size() : ~(size_t)0, got);
+        if (!err.empty()) return fail(P1HIP_ERR_HIP, err);
+      }
+      if (!S.dense) {
+        const std::string err = below_check_candidates(cand_part, got);
+        if (!err.empty()) return fail(P1HIP_ERR_HIP, err);
+        below_sort_hits(got);
+      }
+      for (size_t i = 0; i < got.size() && res.size() < cap; ++i) res.push_back({got[i].key.h, got[i].key.n});
+      add.slices++;
+      add.examined += S.hi - S.lo + 1;
+      if (res.size() == cap || S.hi == upper) return P1HIP_OK;
+      lo = S.hi + 1;
+    }
+  };
+  if ((rc = run()) != P1HIP_OK) {
+    // leave nothing in flight behind a failed call: the next one rewrites the pinned staging tables
+    const std::string keep = g_err;
+    for (Dev& d : R.devs) (void)hipStreamSynchronize(d.stream);
+    g_err = keep;
+    return rc;
+  }
+  for (size_t i = 0; i < res.size(); ++i) hits[i] = res[i];
+  *found = res.size();
+  p1hip_below_stats_t& T = R.lstats;
+  T.calls++;
+  T.slices += add.slices;
+  T.sparse_slices += add.sparse_slices;
+  T.dense_slices += add.dense_slices;
+  T.examined += add.examined;
+  T.scan_nonces += add.scan_nonces;
+  T.mark_nonces += add.mark_nonces;
+  T.candidate_tiles += add.candidate_tiles;
+  T.mark_launches += add.mark_launches;
+  T.hits += res.size();
+  T.wall_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return P1HIP_OK;
+}
+
 }  // namespace
 
 // ----------------------------------------------------------------------------
@@ -1710,6 +1893,26 @@ int p1hip_scan_tiles(const uint8_t* msg, size_t msg_len, uint64_t lower, uint64_
   if (upper - lower > 0xffffffffull) return fail(P1HIP_ERR_ARGS, "more than 2^32 nonces");
   return guarded(
       [&]() { return scan_tiles_locked(msg, msg_len, lower, upper, cap, count, tiles, route, out_hash, out_nonce); });
+}
+
+int p1hip_scan_below(const uint8_t* msg, size_t msg_len, uint64_t lower, uint64_t upper, uint64_t target, size_t cap,
+                     p1hip_result_t* hits, size_t* found) {
+  if (!found || (!hits && cap > 0)) return fail(P1HIP_ERR_ARGS, "null output pointer");
+  if (!msg && msg_len > 0) return fail(P1HIP_ERR_ARGS, "msg == NULL with msg_len > 0");
+  if (msg_len > P1HIP_MAX_MSG_LEN) return fail(P1HIP_ERR_ARGS, "msg_len exceeds P1HIP_MAX_MSG_LEN");
+  if (lower > upper || cap == 0) {
+    *found = 0;
+    return P1HIP_OK;
+  }
+  return guarded([&]() { return scan_below_locked(msg, msg_len, lower, upper, target, cap, hits, found); });
+}
+
+int p1hip_get_below_stats(p1hip_below_stats_t* out) {
+  if (!out) return fail(P1HIP_ERR_ARGS, "null stats pointer");
+  Runtime& R = rt();
+  std::lock_guard<std::mutex> g(R.mu);
+  *out = R.lstats;
+  return P1HIP_OK;
 }
 
 int p1hip_scan_batch(const p1hip_request_t* reqs, size_t n, p1hip_result_t* out) {
@@ -1888,6 +2091,7 @@ void p1hip_reset_stats(void) {
   R.bstats = p1hip_batch_stats_t{};
   R.wstats = p1hip_wide_stats_t{};
   R.astats = p1hip_async_stats_t{};
+  R.lstats = p1hip_below_stats_t{};
   for (Dev& d : R.devs) {
     d.acc = p1hip_device_stats_t{};
     d.acc.shard_first = 1;  // empty until the next scan

@@ -35,6 +35,13 @@
 //
 //   p1miner scan <msg> <lower> <upper>   prints "Result <hash> <nonce>"
 //                                        (the client's output, client.go:59-61)
+//   p1miner scan <msg> <lower> <upper> --below <target> [--count N]
+//                                        every nonce of [lower, upper] whose hash
+//                                        is at or below <target>, the first N of
+//                                        them (default 1), through
+//                                        p1hip_scan_below: one "Result <hash>
+//                                        <nonce>" line per hit in nonce order;
+//                                        exits 0 with no line when there is none
 //   p1miner hash <msg> <nonce>           prints bitcoin.Hash(msg, nonce)
 //   p1miner serve [--device N] [--chunk C] [--batch B [--wide]]
 //                                        one JSON Message per stdin line; every
@@ -81,7 +88,7 @@
 
 static int usage() {
   fprintf(stderr,
-          "usage: p1miner scan <msg> <lower> <upper> | hash <msg> <nonce> | "
+          "usage: p1miner scan <msg> <lower> <upper> [--below <target> [--count N]] | hash <msg> <nonce> | "
           "serve [--device N] [--chunk C] [--batch B [--wide]] | lsp <host:port> [--device N] [--chunk C] [--epoch-limit K] "
           "[--epoch-millis M] [--window W] [--copies K] [--connect-copies K] "
           "[--conns C [--wide] [--linger-us U] [--round-log FILE] [--stats] [--inflight N]] | json | lsp-json | lsp-wrap <connID> <seq> | lsp-unwrap\n");
@@ -96,6 +103,26 @@ static bool parse_u64(const char* s, uint64_t* v) {
   if (errno || *end) return false;
   *v = r;
   return true;
+}
+
+// p1miner scan ... --below <target> [--count N]: the first `count` hits, asked
+// for in calls of at most 2^16 hits, each resuming after the last one's last hit.
+static int run_below(const char* msg, uint64_t lo, uint64_t hi, uint64_t target, uint64_t count) {
+  std::vector<p1hip_result_t> hits((size_t)(count < 65536 ? count : 65536));
+  while (count > 0 && lo <= hi) {
+    const size_t cap = (size_t)(count < hits.size() ? count : hits.size());
+    size_t found = 0;
+    if (p1hip_scan_below((const uint8_t*)msg, strlen(msg), lo, hi, target, cap, hits.data(), &found) != P1HIP_OK) {
+      fprintf(stderr, "p1hip_scan_below: %s\n", p1hip_last_error());
+      return 1;
+    }
+    for (size_t i = 0; i < found; ++i) printf("Result %" PRIu64 " %" PRIu64 "\n", hits[i].hash, hits[i].nonce);
+    if (found < cap || hits[found - 1].nonce == UINT64_MAX) break;
+    count -= found;
+    lo = hits[found - 1].nonce + 1;
+  }
+  p1hip_shutdown();
+  return 0;
 }
 
 // p1miner lsp --conns C: the GPU is open; run the pool (miner_pool.hpp) over
@@ -205,6 +232,18 @@ int main(int argc, char** argv) {
       miner::ScanChunked(argv[2], lo, hi, miner::kDefaultChunk, &h, &n);
       printf("Result %" PRIu64 " %" PRIu64 "\n", h, n);
       return 0;
+    }
+    if (cmd == "scan" && argc > 5) {
+      uint64_t lo, hi, target = 0, count = 1;
+      bool below = false;
+      if (!parse_u64(argv[3], &lo) || !parse_u64(argv[4], &hi)) return usage();
+      for (int i = 5; i < argc; ++i) {
+        if (!strcmp(argv[i], "--below") && i + 1 < argc) { if (!parse_u64(argv[++i], &target)) return usage(); below = true; }
+        else if (!strcmp(argv[i], "--count") && i + 1 < argc) { if (!parse_u64(argv[++i], &count) || count == 0) return usage(); }
+        else return usage();
+      }
+      if (!below) return usage();  // --count means nothing to the minimum scan
+      return run_below(argv[2], lo, hi, target, count);
     }
     if (cmd == "hash" && argc == 4) {
       uint64_t n;

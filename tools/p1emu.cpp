@@ -34,6 +34,24 @@
 //   line comes one line per entry of it, in order:
 //     tile <launch> <tile> <kind> <k> <hash> <nonce> <nruns> {<first> <run_len> <stride> <count>}
 //   the replayed partial and the tile's nonce set from p1_amd/csrc/tile_map.hpp
+//
+// usage: p1emu <msg-hex> <lower> <upper> below=<target> [cap=N] [path=sparse|dense] [maxslice=N]
+//              [minthreads=N] [notable] [nosplit]
+//   replays a whole p1hip_scan_below call on one device: the library's slices,
+//   routes, candidate filter, refine tables and mark decoder
+//   (p1_amd/csrc/below_plan.hpp), the packed-plan replay above for a sparse
+//   slice's partials, and k_below_mark's per-thread function for the marks.
+//   path= and maxslice= stand for P1HIP_BELOW_PATH and P1HIP_BELOW_MAX_SLICE.
+//   prints one "hit <hash> <nonce>" line per hit, then
+//   "below found=<n> slices=<n> sparse=<n> dense=<n> examined=<n> scan_nonces=<n> mark_nonces=<n>
+//    candidate_tiles=<n> mark_launches=<n>"
+// usage: p1emu - <lo> <upper> belowslice=<target>,<want>[,<path>[,<maxslice>]]
+//   the slice rule alone: prints "slice <lo> <hi> <dense>" for the slice that
+//   starts at <lo>
+// usage: p1emu <msg-hex> <lower> <upper> belowdecode=<target>,<thread>
+//   the decoder alone: the true marks of [lower, upper] as one dense table,
+//   with the mark of thread <thread> of the launch inverted; prints
+//   "decoded <hits>" or "error <text>"
 #include <inttypes.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -42,6 +60,7 @@
 #include <string>
 #include <vector>
 
+#include "../p1_amd/csrc/below_plan.hpp"
 #include "../p1_amd/csrc/scan_pack.hpp"
 #include "../p1_amd/csrc/tile_map.hpp"
 #include "scan_replay.hpp"
@@ -100,12 +119,158 @@ static std::vector<uint8_t> unhex(const char* s) {
   return v;
 }
 
+// ---------------------------------------------------------------------------
+// below=: a p1hip_scan_below call on one device
+// ---------------------------------------------------------------------------
+struct BelowOpts {
+  uint64_t target = 0, cap = 1, max_slice = 0, min_threads = kMinFastThreads;
+  int path = kBelowAuto;
+  bool split = true, tabulate = true;
+};
+
+// k_below_mark on the host: kBelowWordsPerTile ballots per tile.
+static std::vector<uint64_t> mark_table(const BelowTable& B, uint64_t target) {
+  std::vector<uint64_t> marks((size_t)B.tiles * kBelowWordsPerTile, 0);
+  const std::vector<BatchSeg>& segs = B.T.segs;
+  for (uint32_t b = 0; b < B.tiles; ++b) {
+    const BatchSeg& S = segs[batch_find_seg(segs.data(), (uint32_t)segs.size(), b)];
+    for (uint32_t t = 0; t < (uint32_t)kBlock; ++t)
+      if (below_thread(S.ga, (uint64_t)(b - S.block0) * kBlock + t, target))
+        marks[(size_t)b * kBelowWordsPerTile + t / 64] |= 1ull << (t % 64);
+  }
+  return marks;
+}
+
+// A sparse slice's pass 1 as run_range runs it: plan, tables, pack, k_scan
+// tile by tile; the tile map and the partials.  "" or an error.
+static std::string below_pass1(const std::vector<uint8_t>& msg, uint64_t lo, uint64_t hi, const BelowOpts& o,
+                               std::vector<TileInfo>& map, std::vector<Key>& part, uint64_t& nonces) {
+  Plan plan;
+  std::string err = make_plan(msg.data(), msg.size(), lo, hi, plan, true, o.min_threads, o.split, o.tabulate);
+  if (!err.empty()) return "plan error: " + err;
+  std::vector<std::vector<uint32_t>> tabs(plan.launches.size());
+  std::vector<uint64_t> tabptr(plan.launches.size(), 0);
+  for (size_t i = 0; i < plan.launches.size(); ++i) {
+    const Launch& L = plan.launches[i];
+    if (!L.fast || (L.mode != 5 && L.mode != 7)) continue;
+    tabs[i] = build_kwtable(L);
+    tabptr[i] = (uint64_t)(uintptr_t)tabs[i].data();
+  }
+  const ScanPack P = pack_scan(plan, kMaxLaunchBlocks);
+  std::vector<Segment> segs(kMaxSegs);
+  part.assign(P.total_blocks, kPoison);
+  ScanCounters ctr;
+  uint32_t part_off = 0;
+  for (const ScanBatch& B : P.batches) {
+    err = fill_segments(plan, P, B, tabptr.data(), segs.data(), ctr);
+    if (!err.empty()) return "segment error: " + err;
+    for (uint32_t b = 0; b < B.blocks; ++b) part[part_off + b] = scan_tile(segs.data(), (uint32_t)B.count, b);
+    part_off += B.blocks;
+  }
+  map = tile_map(plan, P);
+  nonces = ctr.scan_nonces;
+  return map.size() == part.size() ? std::string() : std::string("packing error: map and partials differ in size");
+}
+
+static int run_below(const std::vector<uint8_t>& msg, uint64_t lower, uint64_t upper, const BelowOpts& o) {
+  std::vector<Key> res;
+  uint64_t slices = 0, sparse = 0, dense = 0, examined = 0, scan_nonces = 0, mark_nonces = 0, cands = 0, launches = 0;
+  if (lower <= upper && o.cap > 0) {
+    std::vector<BelowPiece> pieces;
+    std::vector<Key> cand_part;
+    std::vector<BelowHit> got;
+    BelowTable B;
+    for (uint64_t lo = lower;;) {
+      const uint64_t want = o.cap - res.size();
+      const BelowSlice S = below_next_slice(lo, upper, o.target, want, o.path, o.max_slice);
+      pieces.clear();
+      cand_part.clear();
+      got.clear();
+      std::string err;
+      if (S.dense) {
+        below_dense_pieces(S.lo, S.hi, pieces);
+        ++dense;
+      } else {
+        std::vector<TileInfo> map;
+        std::vector<Key> part;
+        uint64_t n = 0;
+        err = below_pass1(msg, S.lo, S.hi, o, map, part, n);
+        if (!err.empty()) {
+          fprintf(stderr, "%s\n", err.c_str());
+          return 1;
+        }
+        scan_nonces += n;
+        for (size_t t = 0; t < map.size(); ++t)
+          if (below_candidate(map[t], part[t], o.target)) {
+            below_tile_pieces(map[t], (uint32_t)cand_part.size(), pieces);
+            cand_part.push_back(part[t]);
+          }
+        ++sparse;
+        cands += cand_part.size();
+      }
+      for (size_t first = 0; first < pieces.size() && (!S.dense || got.size() < want); first += B.count) {
+        err = below_build_table(msg.data(), msg.size(), pieces, first, B);
+        if (err.empty() && (B.count == 0 || B.tiles == 0)) err = "internal: empty refine table";
+        if (err.empty()) {
+          const std::vector<uint64_t> marks = mark_table(B, o.target);
+          ++launches;
+          mark_nonces += B.T.nonces;
+          err = below_decode(B, pieces, marks.data(), o.target, S.dense ? (size_t)(want - got.size()) : ~(size_t)0, got);
+        }
+        if (!err.empty()) {
+          fprintf(stderr, "%s\n", err.c_str());
+          return 1;
+        }
+      }
+      if (!S.dense) {
+        err = below_check_candidates(cand_part, got);
+        if (!err.empty()) {
+          fprintf(stderr, "%s\n", err.c_str());
+          return 1;
+        }
+        below_sort_hits(got);
+      }
+      for (size_t i = 0; i < got.size() && res.size() < o.cap; ++i) res.push_back(got[i].key);
+      ++slices;
+      examined += S.hi - S.lo + 1;
+      if (res.size() == o.cap || S.hi == upper) break;
+      lo = S.hi + 1;
+    }
+  }
+  for (const Key& k : res) printf("hit %" PRIu64 " %" PRIu64 "\n", k.h, k.n);
+  printf("below found=%zu slices=%" PRIu64 " sparse=%" PRIu64 " dense=%" PRIu64 " examined=%" PRIu64
+         " scan_nonces=%" PRIu64 " mark_nonces=%" PRIu64 " candidate_tiles=%" PRIu64 " mark_launches=%" PRIu64 "\n",
+         res.size(), slices, sparse, dense, examined, scan_nonces, mark_nonces, cands, launches);
+  return 0;
+}
+
+static int run_below_decode(const std::vector<uint8_t>& msg, uint64_t lower, uint64_t upper, uint64_t target,
+                            uint64_t thread) {
+  std::vector<BelowPiece> pieces;
+  below_dense_pieces(lower, upper, pieces);
+  BelowTable B;
+  std::string err = below_build_table(msg.data(), msg.size(), pieces, 0, B);
+  if (!err.empty() || B.count != pieces.size() || thread >= (uint64_t)B.tiles * kBlock) {
+    fprintf(stderr, "belowdecode: %s\n", err.empty() ? "range or thread out of one table" : err.c_str());
+    return 2;
+  }
+  std::vector<uint64_t> marks = mark_table(B, target);
+  marks[thread / 64] ^= 1ull << (thread % 64);
+  std::vector<BelowHit> got;
+  err = below_decode(B, pieces, marks.data(), target, ~(size_t)0, got);
+  if (!err.empty()) printf("error %s\n", err.c_str());
+  else printf("decoded %zu\n", got.size());
+  return 0;
+}
+
 int main(int argc, char** argv) {
   if (argc < 4) {
     fprintf(stderr,
             "usage: %s <msg-hex|-> <lower> <upper> [generic|minthreads=N] [nosplit] [notable] "
-            "[packed=MAXBLOCKS[,MAXSEGS]|small] [tiles]\n",
-            argv[0]);
+            "[packed=MAXBLOCKS[,MAXSEGS]|small] [tiles]\n"
+            "       %s <msg-hex|-> <lower> <upper> below=<target> [cap=N] [path=sparse|dense] [maxslice=N] "
+            "[minthreads=N] [notable] [nosplit]\n",
+            argv[0], argv[0]);
     return 2;
   }
   std::vector<uint8_t> msg = strcmp(argv[1], "-") == 0 ? std::vector<uint8_t>() : unhex(argv[1]);
@@ -131,6 +296,42 @@ int main(int argc, char** argv) {
       if (ms > 0 && ms < kMaxSegs) max_segs = (uint32_t)ms;
     }
   }
+  for (int i = 4; i < argc; ++i) {
+    if (strncmp(argv[i], "belowslice=", 11) == 0) {
+      uint64_t v[4] = {0, 1, kBelowAuto, 0};
+      const char* c = argv[i] + 11;
+      for (int j = 0; j < 4 && *c; ++j) {
+        char* end = nullptr;
+        v[j] = strtoull(c, &end, 10);
+        c = *end == ',' ? end + 1 : end;
+      }
+      if (lower > upper || v[1] == 0) return 2;
+      const BelowSlice S = below_next_slice(lower, upper, v[0], v[1], (int)v[2], v[3]);
+      printf("slice %" PRIu64 " %" PRIu64 " %d\n", S.lo, S.hi, (int)S.dense);
+      return 0;
+    }
+    if (strncmp(argv[i], "belowdecode=", 12) == 0) {
+      char* end = nullptr;
+      const uint64_t target = strtoull(argv[i] + 12, &end, 10);
+      if (*end != ',' || lower > upper) return 2;
+      return run_below_decode(msg, lower, upper, target, strtoull(end + 1, nullptr, 10));
+    }
+  }
+  for (int i = 4; i < argc; ++i)
+    if (strncmp(argv[i], "below=", 6) == 0) {
+      BelowOpts o;
+      o.target = strtoull(argv[i] + 6, nullptr, 10);
+      o.min_threads = min_threads;
+      o.split = split;
+      o.tabulate = tabulate;
+      for (int j = 4; j < argc; ++j) {
+        if (strncmp(argv[j], "cap=", 4) == 0) o.cap = strtoull(argv[j] + 4, nullptr, 10);
+        if (strncmp(argv[j], "maxslice=", 9) == 0) o.max_slice = strtoull(argv[j] + 9, nullptr, 10);
+        if (strcmp(argv[j], "path=sparse") == 0) o.path = kBelowSparse;
+        if (strcmp(argv[j], "path=dense") == 0) o.path = kBelowDense;
+      }
+      return run_below(msg, lower, upper, o);
+    }
   if (tiles_out && !packed && !small) {
     fprintf(stderr, "tiles needs packed= or small\n");
     return 2;
