@@ -359,6 +359,103 @@ typedef struct {
 } p1hip_below_stats_t;
 int p1hip_get_below_stats(p1hip_below_stats_t *out);   /* cleared by p1hip_reset_stats */
 
+/* Many target searches in one call.  A pool that hands each worker its own
+ * message and an easy share target asks p1hip_scan_below's question for
+ * hundreds of messages at once, and each answer is a slice of 2^16..2^20
+ * nonces: launch and completion latency on a device that holds about a
+ * thousand workgroups.  Here the current slices of all such requests share one
+ * launch pair per device: k_belowb_mark marks every nonce against its own
+ * request's target and k_belowb_collect, one workgroup per request, turns the
+ * marks into the indices of the request's first hits on the device, so a round
+ * copies back 4 bytes per hit slot instead of one bit per nonce.
+ *
+ * Request i owns hits[off_i .. off_i + cap_i), off_i = the sum of the caps
+ * before it; found[i] entries of that region are written and they are exactly
+ * what p1hip_scan_below(reqs[i]..., cap_i, ...) returns: the hits of the
+ * reference loop in increasing nonce, the first cap_i of them, with the same
+ * found < cap / found == cap meaning.  The result is defined by that loop
+ * alone: rounds, routes, launch pairs and device count never show in it.
+ * The sum of the caps (computed with an overflow check) must be at most
+ * hits_len, otherwise P1HIP_ERR_ARGS.  Every request is validated as
+ * p1hip_scan_below validates it, before anything runs (P1HIP_ERR_ARGS names
+ * the index); `hits` and `found` are untouched on any error.  n == 0, and a
+ * call whose requests are all empty (lower > upper or cap == 0), opens no
+ * device; otherwise lazy init as in p1hip_scan.  Synchronous, serialised under
+ * the library's lock as p1hip_scan_below is; legal while tickets are
+ * outstanding (it owns every buffer it adds, each device's own stream).
+ *
+ * Each request takes one route, fixed from its first slice (the slice rule and
+ * its dense / sparse choice are p1hip_scan_below's; p1hip_below_batch_layout
+ * reports the route):
+ *   0 empty: lower > upper or cap == 0 (found[i] = 0)
+ *   1 coalesced: the first slice is dense and has at most
+ *     P1HIP_BELOW_BATCH_MAX_NONCES nonces.  That admits every cap = 1 request
+ *     at a dense target (2 * 2^64 / 2^46 = 2^19) and cap = 2 at the switch
+ *     target.  Later slices are never longer and stay dense.
+ *   2 individual: every other request, one by one through p1hip_scan_below's
+ *     own path after the coalesced part; these count in p1hip_below_stats_t as
+ *     calls.
+ * The coalesced requests advance in rounds.  A round takes the next slice of
+ * every unfinished request, lays the slices out over the open devices as
+ * p1hip_scan_batch lays its requests out (contiguous groups by tile count, a
+ * request wholly on one device) and cuts a device's group into launch pairs
+ * that close at 2^20 tiles or at P1HIP_BELOW_BATCH_MAX_SLOTS hit slots (a
+ * request's slots in a round: min(hits still wanted, nonces of the slice)).
+ * Every device is enqueued before any is synchronised: one copy back and one
+ * stream synchronisation per device per round.  A request is finished when
+ * found == cap or its slice ended at upper.
+ * Checks kept in the product, a failure of any is P1HIP_ERR_HIP: every
+ * returned index is a thread of its piece; its hash, recomputed on the host,
+ * is at or below the request's target; a request's nonces are strictly
+ * increasing; no request reports more hits than it has slots. */
+#define P1HIP_BELOW_BATCH_MAX_NONCES ((uint64_t)1 << 20)
+#define P1HIP_BELOW_BATCH_MAX_SLOTS ((uint64_t)1 << 22)
+typedef struct {
+  const uint8_t *msg;
+  size_t msg_len;
+  uint64_t lower, upper, target;
+  size_t cap;
+} p1hip_below_request_t;
+int p1hip_scan_below_batch(const p1hip_below_request_t *reqs, size_t n,
+                           p1hip_result_t *hits, size_t hits_len, size_t *found /* n */);
+
+/* Host only (no device): the routes of a call and the layout of its first
+ * round over ndev devices.  route[i]: as above; device[i]: the device of a
+ * coalesced request's first slice (-1 otherwise); tiles[i]: that slice's
+ * workgroup tiles (0 otherwise). */
+int p1hip_below_batch_layout(const p1hip_below_request_t *reqs, size_t n, int ndev,
+                             int32_t *route, int32_t *device, uint32_t *tiles);
+
+/* Accounting of p1hip_scan_below_batch since p1hip_reset_stats.  Individual
+ * requests also count in p1hip_below_stats_t as calls; coalesced ones only
+ * here. */
+typedef struct {
+  uint64_t calls;            /* p1hip_scan_below_batch calls that succeeded       */
+  uint64_t requests;         /* requests in them                                  */
+  uint64_t empty;            /* ... per route: lower > upper or cap == 0          */
+  uint64_t coalesced;        /*     sharing launch pairs                          */
+  uint64_t individual;       /*     run one by one                                */
+  uint64_t rounds;           /* rounds of the coalesced route                     */
+  uint64_t launches;         /* launch pairs (k_belowb_mark + k_belowb_collect)   */
+  uint64_t tiles;            /* workgroups of k_belowb_mark                       */
+  uint64_t mark_nonces;      /* nonces they hashed                                */
+  uint64_t hits;             /* hits returned (all routes)                        */
+  uint64_t bytes_back;       /* bytes copied back from the devices (coalesced)    */
+  double wall_ms;            /* host wall time inside p1hip_scan_below_batch      */
+} p1hip_below_batch_stats_t;
+int p1hip_get_below_batch_stats(p1hip_below_batch_stats_t *out);   /* cleared by p1hip_reset_stats */
+
+/* Test hook: k_belowb_collect alone, on the first device, over crafted mark
+ * words.  Request r of nreq owns words [4 * req_tile0[r], 4 * req_tile0[r + 1])
+ * of `words` and slots [req_hit0[r], req_hit0[r + 1]) of `idx` (both tables
+ * have nreq + 1 entries, start at 0 and never fall; at most 2^20 tiles and
+ * P1HIP_BELOW_BATCH_MAX_SLOTS slots).  idx receives, per request, the thread
+ * indices (64 * word + bit) of its first set bits in word and bit order, as
+ * many as it has slots; count[r] their number; slots the kernel does not
+ * write read UINT32_MAX.  Counts in no statistics. */
+int p1hip_below_collect(const uint64_t *words, const uint32_t *req_tile0, const uint32_t *req_hit0,
+                        size_t nreq, uint32_t *idx, uint32_t *count);
+
 /* Kernel-level accounting.  One p1hip_scan = one (rarely several) launch of
  * the scan kernel k_scan per device, covering every decade of the range; a
  * share of at most 2^16 nonces is one launch of k_scan_small instead (plan in
@@ -450,8 +547,11 @@ int p1hip_comm_info(int index, int *nranks, int *rank);
  * p1hip_scan_tiles and its p1hip_tile_t, and with p1hip_batch_submit,
  * p1hip_batch_wait, p1hip_get_async_stats, p1hip_async_stats_t and
  * P1HIP_ERR_BUSY, and with p1hip_scan_below, p1hip_get_below_stats,
- * p1hip_below_stats_t and the P1HIP_BELOW_* constants: purely additive, the
- * layout of every existing struct is unchanged. */
+ * p1hip_below_stats_t and the P1HIP_BELOW_* constants, and with
+ * p1hip_scan_below_batch, p1hip_below_batch_layout,
+ * p1hip_get_below_batch_stats, the test hook p1hip_below_collect and their
+ * structs: purely additive, the layout of every existing struct is
+ * unchanged. */
 #define P1HIP_ABI_VERSION 6
 int p1hip_abi_version(void);
 

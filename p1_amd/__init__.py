@@ -52,5 +52,13 @@ from ._lib import (  # noqa: F401
     BELOW_MAX_SLICE,
     BELOW_MAX_SLICE_DENSE,
     BELOW_DENSE_TARGET,
+    scan_below_batch,
+    below_batch_layout,
+    get_below_batch_stats,
+    below_collect,
+    belowb_codeobj_sha256,
+    BELOW_BATCH_MAX_NONCES,
+    BELOW_BATCH_MAX_SLOTS,
+    BELOW_BATCH_ROUTES,
 )
 from .sharding import shard_range, combine_keys  # noqa: F401

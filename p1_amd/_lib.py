@@ -142,6 +142,31 @@ class BelowStats(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class BelowRequest(ctypes.Structure):
+    _fields_ = [("msg", ctypes.c_char_p), ("msg_len", ctypes.c_size_t), ("lower", U64), ("upper", U64),
+                ("target", U64), ("cap", ctypes.c_size_t)]
+
+
+class BelowBatchStats(ctypes.Structure):
+    _fields_ = [
+        ("calls", U64),
+        ("requests", U64),
+        ("empty", U64),
+        ("coalesced", U64),
+        ("individual", U64),
+        ("rounds", U64),
+        ("launches", U64),
+        ("tiles", U64),
+        ("mark_nonces", U64),
+        ("hits", U64),
+        ("bytes_back", U64),
+        ("wall_ms", ctypes.c_double),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class DeviceInfo(ctypes.Structure):
     _fields_ = [
         ("ordinal", ctypes.c_int32),
@@ -212,6 +237,16 @@ SIGNATURES = [
      [ctypes.c_char_p, ctypes.c_size_t, U64, U64, U64, ctypes.c_size_t, ctypes.POINTER(Result),
       ctypes.POINTER(ctypes.c_size_t)]),
     ("p1hip_get_below_stats", ctypes.c_int, [ctypes.POINTER(BelowStats)]),
+    ("p1hip_scan_below_batch", ctypes.c_int,
+     [ctypes.POINTER(BelowRequest), ctypes.c_size_t, ctypes.POINTER(Result), ctypes.c_size_t,
+      ctypes.POINTER(ctypes.c_size_t)]),
+    ("p1hip_below_batch_layout", ctypes.c_int,
+     [ctypes.POINTER(BelowRequest), ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(ctypes.c_int32),
+      ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_uint32)]),
+    ("p1hip_get_below_batch_stats", ctypes.c_int, [ctypes.POINTER(BelowBatchStats)]),
+    ("p1hip_below_collect", ctypes.c_int,
+     [ctypes.POINTER(U64), ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32), ctypes.c_size_t,
+      ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]),
     ("p1hip_hash", ctypes.c_int, [ctypes.c_char_p, ctypes.c_size_t, U64, ctypes.POINTER(U64)]),
     ("p1hip_plan_shards", ctypes.c_int,
      [ctypes.c_char_p, ctypes.c_size_t, U64, U64, ctypes.c_int, ctypes.POINTER(U64), ctypes.POINTER(U64)]),
@@ -432,6 +467,89 @@ def get_below_stats():
     s = BelowStats()
     _check(load().p1hip_get_below_stats(ctypes.byref(s)))
     return s.as_dict()
+
+
+# include/p1hip.h P1HIP_BELOW_BATCH_MAX_NONCES, P1HIP_BELOW_BATCH_MAX_SLOTS
+BELOW_BATCH_MAX_NONCES = 1 << 20
+BELOW_BATCH_MAX_SLOTS = 1 << 22
+BELOW_BATCH_ROUTES = ("empty", "coalesced", "individual")
+
+
+def _below_requests(requests):
+    """(array of BelowRequest, the rows it borrows its messages from) for an
+    iterable of (msg, lower, upper, target, cap)."""
+    rows = [(_bytes(m), int(lo), int(hi), int(t), int(cap)) for m, lo, hi, t, cap in requests]
+    arr = (BelowRequest * max(len(rows), 1))()
+    for r, (m, lo, hi, t, cap) in zip(arr, rows):
+        r.msg, r.msg_len, r.lower, r.upper, r.target, r.cap = m, len(m), lo, hi, t, cap
+    return arr, rows
+
+
+def scan_below_batch(requests):
+    """p1hip_scan_below_batch: `requests` is an iterable of (msg, lower, upper,
+    target, cap); returns one list per request, in order, each exactly what
+    scan_below(msg, lower, upper, target, cap) returns.  The requests whose
+    slices are dense and of at most 2^20 nonces share launch pairs."""
+    arr, rows = _below_requests(requests)
+    n = len(rows)
+    total = sum(r[4] for r in rows)
+    hits = (Result * max(total, 1))()
+    found = (ctypes.c_size_t * max(n, 1))()
+    _check(load().p1hip_scan_below_batch(arr, n, hits, total, found))
+    out, off = [], 0
+    for i in range(n):
+        out.append([(hits[off + k].hash, hits[off + k].nonce) for k in range(found[i])])
+        off += rows[i][4]
+    return out
+
+
+def below_batch_layout(requests, ndev):
+    """p1hip_below_batch_layout: per request {"route" (one of
+    BELOW_BATCH_ROUTES), "device", "tiles"} of scan_below_batch's first round
+    over `ndev` devices (device -1 and tiles 0 unless coalesced).  Host-only."""
+    arr, rows = _below_requests(requests)
+    n = len(rows)
+    route, device = (ctypes.c_int32 * max(n, 1))(), (ctypes.c_int32 * max(n, 1))()
+    tiles = (ctypes.c_uint32 * max(n, 1))()
+    _check(load().p1hip_below_batch_layout(arr, n, int(ndev), route, device, tiles))
+    return [{"route": BELOW_BATCH_ROUTES[route[i]], "device": device[i], "tiles": tiles[i]} for i in range(n)]
+
+
+def get_below_batch_stats():
+    """Accounting of scan_below_batch since reset_stats (p1hip_get_below_batch_stats)."""
+    s = BelowBatchStats()
+    _check(load().p1hip_get_below_batch_stats(ctypes.byref(s)))
+    return s.as_dict()
+
+
+def below_collect(words, req_tile0, req_hit0):
+    """p1hip_below_collect (test hook): k_belowb_collect alone over the mark
+    words `words`; request r owns words [4 * req_tile0[r], 4 * req_tile0[r + 1])
+    and slots [req_hit0[r], req_hit0[r + 1]).  Returns (idx, count): every slot
+    (UINT32_MAX where the kernel wrote nothing) and the hits per request."""
+    nreq = len(req_tile0) - 1
+    assert nreq >= 0 and len(req_hit0) == nreq + 1 and len(words) == 4 * req_tile0[-1]
+    wa = (U64 * max(len(words), 1))(*words)
+    ta = (ctypes.c_uint32 * (nreq + 1))(*req_tile0)
+    ha = (ctypes.c_uint32 * (nreq + 1))(*req_hit0)
+    idx = (ctypes.c_uint32 * max(req_hit0[-1], 1))()
+    count = (ctypes.c_uint32 * max(nreq, 1))()
+    _check(load().p1hip_below_collect(wa, ta, ha, nreq, idx, count))
+    return list(idx[:req_hit0[-1]]), list(count[:nreq])
+
+
+def belowb_codeobj_sha256(lib=None):
+    """sha256 (hex) of the fourth embedded code object, the kernels of
+    scan_below_batch (p1hip_belowb_co .. p1hip_belowb_co_end of
+    csrc/p1hip_belowb_blob.S)."""
+    import hashlib
+
+    lib = lib or load()
+    start = ctypes.addressof(ctypes.c_char.in_dll(lib, "p1hip_belowb_co"))
+    end = ctypes.addressof(ctypes.c_char.in_dll(lib, "p1hip_belowb_co_end"))
+    if end <= start:
+        raise P1HipError(-100, "embedded below batch code object is empty")
+    return hashlib.sha256(ctypes.string_at(start, end - start)).hexdigest()
 
 
 def below_codeobj_sha256(lib=None):

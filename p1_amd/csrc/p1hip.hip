@@ -42,9 +42,18 @@
 // Slices, filter, tables and decoder come from below_plan.hpp, which
 // tools/p1emu shares.
 //
+// p1hip_scan_below_batch: many target searches in one call.  The requests
+// whose slices are dense and of at most 2^20 nonces advance in rounds; a round
+// lays the current slice of each over the devices and launch pairs,
+// k_belowb_mark marks them against each request's own target and
+// k_belowb_collect turns the marks into hit indices on the device (a fourth
+// code object, p1hip_belowb_kernels.hip, p1hip_belowb_blob.S).  Routes, round
+// layout, tables and decoder come from belowb_plan.hpp, which tools/batch_emu
+// shares.
+//
 // Order of this file: runtime state, helpers, the scan path, the batch path,
-// the wide path, submit / wait, reduce_pairs, scan_tiles, scan_below, then the
-// C ABI in one extern "C" block.  Every HIP and RCCL
+// the wide path, submit / wait, reduce_pairs, scan_tiles, scan_below,
+// scan_below_batch, then the C ABI in one extern "C" block.  Every HIP and RCCL
 // call of the library is in this file (tests/test_stream_discipline.py).
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -67,6 +76,7 @@
 #include "async_slots.hpp"
 #include "batch_plan.hpp"
 #include "below_plan.hpp"
+#include "belowb_plan.hpp"
 #include "planner.hpp"
 #include "scan_abi.hpp"
 #include "scan_pack.hpp"
@@ -74,10 +84,11 @@
 #include "wide_plan.hpp"
 
 // the embedded gfx950 code objects (p1hip_kernels_blob.S, p1hip_batch_blob.S,
-// p1hip_below_blob.S)
+// p1hip_below_blob.S, p1hip_belowb_blob.S)
 extern "C" const unsigned char p1hip_kernels_co[];
 extern "C" const unsigned char p1hip_batch_co[];
 extern "C" const unsigned char p1hip_below_co[];
+extern "C" const unsigned char p1hip_belowb_co[];
 
 using namespace p1;
 
@@ -348,6 +359,22 @@ struct Dev {
   PinnedBuf<BatchSeg> h_mseg;
   DevBuf<uint64_t> d_marks;     // kBelowWordsPerTile words per tile
   PinnedBuf<uint64_t> h_marks;
+  // p1hip_scan_below_batch: its own code object and buffers.  The tables of
+  // every launch pair of a round lie at their own offsets; the marks are one
+  // launch pair's (the pairs of a device run in stream order); d_qout holds,
+  // per launch pair, its requests' counts and then their hit indices, and is
+  // copied back once per round.
+  hipModule_t qmod = nullptr;
+  hipFunction_t f_qmark = nullptr, f_qcollect = nullptr;
+  DevBuf<BatchSeg> d_qseg;
+  PinnedBuf<BatchSeg> h_qseg;
+  DevBuf<uint64_t> d_qtarget;
+  PinnedBuf<uint64_t> h_qtarget;
+  DevBuf<uint32_t> d_qtab;      // per launch pair: req_tile0 (nreq + 1), req_hit0 (nreq + 1)
+  PinnedBuf<uint32_t> h_qtab;
+  DevBuf<uint64_t> d_qmarks;    // kBelowWordsPerTile words per tile
+  DevBuf<uint32_t> d_qout;
+  PinnedBuf<uint32_t> h_qout;
   SlotDev slot[P1HIP_MAX_INFLIGHT];  // p1hip_batch_submit: one buffer set per ticket slot
   std::vector<hipEvent_t> evs;  // profiling event pool (pairs)
   // MODE 5 K+W tables on this device, least recently used first (built by
@@ -413,6 +440,7 @@ struct Runtime {
   p1hip_batch_stats_t bstats{};
   p1hip_wide_stats_t wstats{};
   p1hip_below_stats_t lstats{};
+  p1hip_below_batch_stats_t qstats{};
 };
 
 // Never destroyed: the runtime state outlives every static destructor, so a
@@ -509,6 +537,7 @@ int dev_release(Dev& d) {
   if (d.mod) (void)hipModuleUnload(d.mod);
   if (d.bmod) (void)hipModuleUnload(d.bmod);
   if (d.lmod) (void)hipModuleUnload(d.lmod);
+  if (d.qmod) (void)hipModuleUnload(d.qmod);
   d = Dev();  // every Buf frees itself here: this device is current, its work is done
   return 0;
 }
@@ -565,6 +594,9 @@ int init_devs(Runtime& R, const std::vector<int>& ords) {
     HIPCHK(hipModuleGetFunction(&d.f_wreduce, d.bmod, "k_wide_reduce"));
     HIPCHK(hipModuleLoadData(&d.lmod, p1hip_below_co));
     HIPCHK(hipModuleGetFunction(&d.f_mark, d.lmod, "k_below_mark"));
+    HIPCHK(hipModuleLoadData(&d.qmod, p1hip_belowb_co));
+    HIPCHK(hipModuleGetFunction(&d.f_qmark, d.qmod, "k_belowb_mark"));
+    HIPCHK(hipModuleGetFunction(&d.f_qcollect, d.qmod, "k_belowb_collect"));
     // fixed-size buffers: floor = need, so exactly that many elements
     HIPCHK(d.d_small_part.reserve(kSmallMaxBlocks, kSmallMaxBlocks));
     HIPCHK(d.d_ticket.reserve(1, 1));
@@ -1757,17 +1789,16 @@ int below_filter(Runtime& R, const uint8_t* msg, size_t msg_len, uint64_t lo, ui
   return P1HIP_OK;
 }
 
-int scan_below_locked(const uint8_t* msg, size_t msg_len, uint64_t lower, uint64_t upper, uint64_t target, size_t cap,
-                      p1hip_result_t* hits, size_t* found) {
-  Runtime& R = rt();
-  std::lock_guard<std::mutex> g(R.mu);
+// One p1hip_scan_below with R.mu held by the caller (p1hip_scan_below;
+// p1hip_scan_below_batch for its individual requests): the hits go to `res`
+// (empty on entry), which holds the whole answer only when the call succeeds.
+int scan_below_held(Runtime& R, const uint8_t* msg, size_t msg_len, uint64_t lower, uint64_t upper, uint64_t target,
+                    size_t cap, std::vector<p1hip_result_t>& res) {
   const auto t0 = std::chrono::steady_clock::now();
   int rc = ensure_init(R);
   if (rc) return rc;
   const int path = (int)knob(kBelowPathKnob);
   const uint64_t max_slice = knob(kBelowMaxSliceKnob);
-  // results are gathered here and copied to `hits` only when the whole call has succeeded
-  std::vector<p1hip_result_t> res;
   p1hip_below_stats_t add{};
   auto run = [&]() -> int {
     std::vector<BelowPiece> pieces;
@@ -1819,8 +1850,6 @@ int scan_below_locked(const uint8_t* msg, size_t msg_len, uint64_t lower, uint64
     g_err = keep;
     return rc;
   }
-  for (size_t i = 0; i < res.size(); ++i) hits[i] = res[i];
-  *found = res.size();
   p1hip_below_stats_t& T = R.lstats;
   T.calls++;
   T.slices += add.slices;
@@ -1833,6 +1862,256 @@ int scan_below_locked(const uint8_t* msg, size_t msg_len, uint64_t lower, uint64
   T.mark_launches += add.mark_launches;
   T.hits += res.size();
   T.wall_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return P1HIP_OK;
+}
+
+int scan_below_locked(const uint8_t* msg, size_t msg_len, uint64_t lower, uint64_t upper, uint64_t target, size_t cap,
+                      p1hip_result_t* hits, size_t* found) {
+  Runtime& R = rt();
+  std::lock_guard<std::mutex> g(R.mu);
+  // results are gathered here and copied to `hits` only when the whole call has succeeded
+  std::vector<p1hip_result_t> res;
+  if (int rc = scan_below_held(R, msg, msg_len, lower, upper, target, cap, res)) return rc;
+  for (size_t i = 0; i < res.size(); ++i) hits[i] = res[i];
+  *found = res.size();
+  return P1HIP_OK;
+}
+
+// ----------------------------------------------------------------------------
+// p1hip_scan_below_batch
+// ----------------------------------------------------------------------------
+// the public header restates belowb_abi.hpp's constants
+static_assert(P1HIP_BELOW_BATCH_MAX_NONCES == kBelowBatchMaxNonces && P1HIP_BELOW_BATCH_MAX_SLOTS == kBelowBatchMaxSlots,
+              "p1hip.h and belowb_abi.hpp disagree");
+
+int below_batch_check(const p1hip_below_request_t* reqs, size_t n) {
+  for (size_t i = 0; i < n; ++i) {
+    if (!reqs[i].msg && reqs[i].msg_len > 0)
+      return fail(P1HIP_ERR_ARGS, "request " + std::to_string(i) + ": msg == NULL with msg_len > 0");
+    if (reqs[i].msg_len > P1HIP_MAX_MSG_LEN)
+      return fail(P1HIP_ERR_ARGS, "request " + std::to_string(i) + ": msg_len exceeds P1HIP_MAX_MSG_LEN");
+  }
+  return P1HIP_OK;
+}
+
+std::vector<BelowBReq> below_batch_reqs(const p1hip_below_request_t* reqs, size_t n) {
+  std::vector<BelowBReq> q(n);
+  for (size_t i = 0; i < n; ++i)
+    q[i] = {reqs[i].msg, reqs[i].msg_len, reqs[i].lower, reqs[i].upper, reqs[i].target, (uint64_t)reqs[i].cap};
+  return q;
+}
+
+// Where one launch pair's tables and results lie in its device's buffers
+// (elements): segments, targets, the two request tables, counts + indices.
+struct BelowBPlace {
+  size_t seg0, req0, tab0, out0;
+};
+
+// Enqueue launch pair (L, B) on device d's stream: the tables, k_belowb_mark,
+// k_belowb_collect.  No copy back (one per device per round follows the
+// device's last pair) and no synchronisation.  Workgroup b of the L.tiles
+// marked writes words [4b, 4b + 4) of d_qmarks, every one of them, and request
+// r's collect workgroup reads only words of its own tiles, so the marks are
+// not cleared first; the device's next pair reuses them in stream order.
+int below_batch_enqueue(Dev& d, const BelowBLaunch& L, const BelowBTable& B, const BelowBPlace& P) {
+  const size_t nseg = B.T.segs.size(), nreq = L.items.size();
+  memcpy(d.h_qseg.p + P.seg0, B.T.segs.data(), nseg * sizeof(BatchSeg));
+  memcpy(d.h_qtarget.p + P.req0, B.targets.data(), nreq * sizeof(uint64_t));
+  memcpy(d.h_qtab.p + P.tab0, B.T.req_tile0.data(), (nreq + 1) * sizeof(uint32_t));
+  memcpy(d.h_qtab.p + P.tab0 + nreq + 1, B.req_hit0.data(), (nreq + 1) * sizeof(uint32_t));
+  HIPCHK(hipMemcpyAsync(d.d_qseg.p + P.seg0, d.h_qseg.p + P.seg0, nseg * sizeof(BatchSeg), hipMemcpyHostToDevice,
+                        d.stream));
+  HIPCHK(hipMemcpyAsync(d.d_qtarget.p + P.req0, d.h_qtarget.p + P.req0, nreq * sizeof(uint64_t), hipMemcpyHostToDevice,
+                        d.stream));
+  HIPCHK(hipMemcpyAsync(d.d_qtab.p + P.tab0, d.h_qtab.p + P.tab0, 2 * (nreq + 1) * sizeof(uint32_t),
+                        hipMemcpyHostToDevice, d.stream));
+  HIPCHK(launch(d.f_qmark, L.tiles, kBlock, d.stream, (const BatchSeg*)(d.d_qseg.p + P.seg0), (uint32_t)nseg,
+                (const uint64_t*)(d.d_qtarget.p + P.req0), d.d_qmarks.p));
+  HIPCHK(launch(d.f_qcollect, (uint32_t)nreq, kBlock, d.stream, (const uint64_t*)d.d_qmarks.p,
+                (const uint32_t*)(d.d_qtab.p + P.tab0), (const uint32_t*)(d.d_qtab.p + P.tab0 + nreq + 1),
+                d.d_qout.p + P.out0 + nreq, d.d_qout.p + P.out0));
+  return P1HIP_OK;
+}
+
+int scan_below_batch_locked(const p1hip_below_request_t* reqs, size_t n, const std::vector<size_t>& off,
+                            p1hip_result_t* hits, size_t* found) {
+  Runtime& R = rt();
+  std::lock_guard<std::mutex> g(R.mu);
+  const auto t0 = std::chrono::steady_clock::now();
+  const int path = (int)knob(kBelowPathKnob);
+  const uint64_t max_slice = knob(kBelowMaxSliceKnob);
+  const std::vector<BelowBReq> q = below_batch_reqs(reqs, n);
+  p1hip_below_batch_stats_t add{};
+  std::vector<size_t> coalesced, individual;
+  for (size_t i = 0; i < n; ++i) {
+    const int route = belowb_route(q[i], path, max_slice);
+    if (route == kBelowBCoalesced) coalesced.push_back(i);
+    else if (route == kBelowBIndividual) individual.push_back(i);
+    else add.empty++;
+  }
+  // results are gathered here and copied to `hits` only when the whole call has succeeded
+  std::vector<std::vector<p1hip_result_t>> res(n);
+  int rc;
+  auto run = [&]() -> int {
+    if (coalesced.empty() && individual.empty()) return P1HIP_OK;  // all empty: no device
+    if ((rc = ensure_init(R))) return rc;
+    const int ndev = (int)R.devs.size();
+    std::vector<BelowBState> st(coalesced.size());
+    for (size_t j = 0; j < coalesced.size(); ++j) st[j] = {q[coalesced[j]].lower, 0, false};
+    std::vector<BelowBItem> items;
+    std::vector<BelowBTable> tabs;
+    std::vector<BelowBPlace> place;
+    std::vector<std::vector<Key>> got;
+    for (size_t left = coalesced.size(); left > 0;) {
+      std::string err = belowb_round_items(q.data(), coalesced, st, path, max_slice, items);
+      if (!err.empty()) return fail(P1HIP_ERR_HIP, err);
+      const std::vector<BelowBLaunch> launches = belowb_layout(items, ndev);
+      // every table of the round, then each device's buffers (its stream is
+      // idle: every round ends with a synchronisation), then the enqueues
+      tabs.resize(launches.size());
+      place.resize(launches.size());
+      std::vector<BelowBPlace> need((size_t)ndev, BelowBPlace{0, 0, 0, 0});
+      std::vector<size_t> max_tiles((size_t)ndev, 0);
+      for (size_t l = 0; l < launches.size(); ++l) {
+        const BelowBLaunch& L = launches[l];
+        err = belowb_build_table(q.data(), coalesced, items, L, tabs[l]);
+        if (!err.empty()) return fail(P1HIP_ERR_ARGS, err);
+        if (L.tiles == 0 || L.tiles > kBatchMaxTiles || L.slots > kBelowBatchMaxSlots)
+          return fail(P1HIP_ERR_HIP, "internal: a below batch launch pair outside its limits");
+        BelowBPlace& N = need[(size_t)L.device];
+        place[l] = N;
+        N.seg0 += tabs[l].T.segs.size();
+        N.req0 += L.items.size();
+        N.tab0 += 2 * (L.items.size() + 1);
+        N.out0 += L.items.size() + (size_t)L.slots;
+        if (L.tiles > max_tiles[(size_t)L.device]) max_tiles[(size_t)L.device] = L.tiles;
+      }
+      for (int i = 0; i < ndev; ++i) {
+        const BelowBPlace& N = need[(size_t)i];
+        if (N.req0 == 0) continue;
+        Dev& d = R.devs[(size_t)i];
+        HIPCHK(hipSetDevice(d.ordinal));
+        HIPCHK(d.d_qseg.reserve(N.seg0, 64));
+        HIPCHK(d.h_qseg.reserve(N.seg0, 64));
+        HIPCHK(d.d_qtarget.reserve(N.req0, 64));
+        HIPCHK(d.h_qtarget.reserve(N.req0, 64));
+        HIPCHK(d.d_qtab.reserve(N.tab0, 128));
+        HIPCHK(d.h_qtab.reserve(N.tab0, 128));
+        HIPCHK(d.d_qmarks.reserve(max_tiles[(size_t)i] * kBelowWordsPerTile, 4096));
+        HIPCHK(d.d_qout.reserve(N.out0, 1024));
+        HIPCHK(d.h_qout.reserve(N.out0, 1024));
+      }
+      for (size_t l = 0; l < launches.size(); ++l) {
+        const BelowBLaunch& L = launches[l];
+        Dev& d = R.devs[(size_t)L.device];
+        HIPCHK(hipSetDevice(d.ordinal));
+        if ((rc = below_batch_enqueue(d, L, tabs[l], place[l])) != P1HIP_OK) return rc;
+        add.launches++;
+        add.tiles += L.tiles;
+        add.mark_nonces += tabs[l].T.nonces;
+        // the device's last pair of the round: the one copy back
+        if (l + 1 == launches.size() || launches[l + 1].device != L.device) {
+          const size_t words = need[(size_t)L.device].out0;
+          HIPCHK(hipMemcpyAsync(d.h_qout.p, d.d_qout.p, words * sizeof(uint32_t), hipMemcpyDeviceToHost, d.stream));
+          add.bytes_back += words * sizeof(uint32_t);
+        }
+      }
+      for (int i = 0; i < ndev; ++i)
+        if (need[(size_t)i].req0) {
+          Dev& d = R.devs[(size_t)i];
+          HIPCHK(hipSetDevice(d.ordinal));
+          HIPCHK(hipStreamSynchronize(d.stream));
+        }
+      for (size_t l = 0; l < launches.size(); ++l) {
+        const BelowBLaunch& L = launches[l];
+        const uint32_t* out = R.devs[(size_t)L.device].h_qout.p + place[l].out0;
+        err = belowb_decode(tabs[l], out + L.items.size(), out, got);
+        if (!err.empty()) return fail(P1HIP_ERR_HIP, err);
+        for (size_t r = 0; r < L.items.size(); ++r) {
+          const BelowBItem& it = items[L.items[r]];
+          BelowBState& S = st[it.req];
+          const size_t i = coalesced[it.req];
+          for (const Key& k : got[r]) {
+            if (!res[i].empty() && k.n <= res[i].back().nonce)
+              return fail(P1HIP_ERR_HIP, "collect check: request " + std::to_string(i) + " has nonces out of order");
+            res[i].push_back({k.h, k.n});
+          }
+          S.found += got[r].size();
+          if (S.found == q[i].cap || it.hi == q[i].upper) {
+            S.done = true;
+            --left;
+          } else {
+            S.lo = it.hi + 1;
+          }
+        }
+      }
+      add.rounds++;
+    }
+    // The other requests: one by one through p1hip_scan_below's own path.
+    for (size_t i : individual)
+      if ((rc = scan_below_held(R, q[i].msg, q[i].len, q[i].lower, q[i].upper, q[i].target, (size_t)q[i].cap, res[i])))
+        return fail(rc, "request " + std::to_string(i) + ": " + g_err);
+    return P1HIP_OK;
+  };
+  if ((rc = run()) != P1HIP_OK) {
+    // leave no launch pair in flight behind a failed call: the next call
+    // rewrites the pinned staging tables
+    const std::string keep = g_err;
+    for (Dev& d : R.devs) (void)hipStreamSynchronize(d.stream);
+    g_err = keep;
+    return rc;
+  }
+  for (size_t i = 0; i < n; ++i) {
+    for (size_t k = 0; k < res[i].size(); ++k) hits[off[i] + k] = res[i][k];
+    found[i] = res[i].size();
+    add.hits += res[i].size();
+  }
+  p1hip_below_batch_stats_t& T = R.qstats;
+  T.calls++;
+  T.requests += n;
+  T.empty += add.empty;
+  T.coalesced += coalesced.size();
+  T.individual += individual.size();
+  T.rounds += add.rounds;
+  T.launches += add.launches;
+  T.tiles += add.tiles;
+  T.mark_nonces += add.mark_nonces;
+  T.hits += add.hits;
+  T.bytes_back += add.bytes_back;
+  T.wall_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return P1HIP_OK;
+}
+
+// p1hip_below_collect (test hook): k_belowb_collect alone on the first device,
+// in scratch of exactly this call's size, as reduce_pairs_locked's.
+int below_collect_locked(const uint64_t* words, const uint32_t* req_tile0, const uint32_t* req_hit0, size_t nreq,
+                         uint32_t* idx, uint32_t* count) {
+  Runtime& R = rt();
+  std::lock_guard<std::mutex> g(R.mu);
+  int rc = ensure_init(R);
+  if (rc) return rc;
+  Dev& d = R.devs[0];
+  HIPCHK(hipSetDevice(d.ordinal));
+  const size_t nwords = (size_t)req_tile0[nreq] * kBelowWordsPerTile, nslots = req_hit0[nreq];
+  DevBuf<uint64_t> dm;
+  DevBuf<uint32_t> dt, dx, dc;
+  HIPCHK(dm.reserve(nwords + 1, nwords + 1));
+  HIPCHK(dt.reserve(2 * (nreq + 1), 2 * (nreq + 1)));
+  HIPCHK(dx.reserve(nslots + 1, nslots + 1));
+  HIPCHK(dc.reserve(nreq, nreq));
+  if (nwords) HIPCHK(hipMemcpyAsync(dm.p, words, nwords * sizeof(uint64_t), hipMemcpyHostToDevice, d.stream));
+  HIPCHK(hipMemcpyAsync(dt.p, req_tile0, (nreq + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, d.stream));
+  HIPCHK(hipMemcpyAsync(dt.p + nreq + 1, req_hit0, (nreq + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, d.stream));
+  // only for the hook: a slot the kernel leaves alone reads UINT32_MAX
+  HIPCHK(hipMemsetAsync(dx.p, 0xff, (nslots + 1) * sizeof(uint32_t), d.stream));
+  HIPCHK(launch(d.f_qcollect, (uint32_t)nreq, kBlock, d.stream, (const uint64_t*)dm.p, (const uint32_t*)dt.p,
+                (const uint32_t*)(dt.p + nreq + 1), dx.p, dc.p));
+  std::vector<uint32_t> hx(nslots), hc(nreq);
+  if (nslots) HIPCHK(hipMemcpyAsync(hx.data(), dx.p, nslots * sizeof(uint32_t), hipMemcpyDeviceToHost, d.stream));
+  HIPCHK(hipMemcpyAsync(hc.data(), dc.p, nreq * sizeof(uint32_t), hipMemcpyDeviceToHost, d.stream));
+  HIPCHK(hipStreamSynchronize(d.stream));
+  for (size_t i = 0; i < nslots; ++i) idx[i] = hx[i];
+  for (size_t i = 0; i < nreq; ++i) count[i] = hc[i];
   return P1HIP_OK;
 }
 
@@ -1913,6 +2192,81 @@ int p1hip_get_below_stats(p1hip_below_stats_t* out) {
   std::lock_guard<std::mutex> g(R.mu);
   *out = R.lstats;
   return P1HIP_OK;
+}
+
+int p1hip_scan_below_batch(const p1hip_below_request_t* reqs, size_t n, p1hip_result_t* hits, size_t hits_len,
+                           size_t* found) {
+  if (n == 0) return P1HIP_OK;
+  if (!reqs || !found) return fail(P1HIP_ERR_ARGS, "null request or found array");
+  return guarded([&]() {
+    if (int rc = below_batch_check(reqs, n)) return rc;
+    std::vector<size_t> off(n);
+    size_t total = 0;
+    for (size_t i = 0; i < n; ++i) {
+      off[i] = total;
+      if (__builtin_add_overflow(total, reqs[i].cap, &total))
+        return fail(P1HIP_ERR_ARGS, "request " + std::to_string(i) + ": the sum of the caps overflows");
+    }
+    if (total > hits_len)
+      return fail(P1HIP_ERR_ARGS, "the caps add up to " + std::to_string(total) + ", hits_len is " + std::to_string(hits_len));
+    if (!hits && total > 0) return fail(P1HIP_ERR_ARGS, "null hits array");
+    return scan_below_batch_locked(reqs, n, off, hits, found);
+  });
+}
+
+int p1hip_below_batch_layout(const p1hip_below_request_t* reqs, size_t n, int ndev, int32_t* route, int32_t* device,
+                             uint32_t* tiles) {
+  if (ndev <= 0) return fail(P1HIP_ERR_ARGS, "ndev <= 0");
+  if (n == 0) return P1HIP_OK;
+  if (!reqs || !route || !device || !tiles) return fail(P1HIP_ERR_ARGS, "null request or output array");
+  return guarded([&]() {
+    if (int rc = below_batch_check(reqs, n)) return rc;
+    const int path = (int)knob(kBelowPathKnob);
+    const uint64_t max_slice = knob(kBelowMaxSliceKnob);
+    const std::vector<BelowBReq> q = below_batch_reqs(reqs, n);
+    std::vector<size_t> coalesced;
+    for (size_t i = 0; i < n; ++i) {
+      route[i] = belowb_route(q[i], path, max_slice);
+      device[i] = -1;
+      tiles[i] = 0;
+      if (route[i] == kBelowBCoalesced) coalesced.push_back(i);
+    }
+    std::vector<BelowBState> st(coalesced.size());
+    for (size_t j = 0; j < coalesced.size(); ++j) st[j] = {q[coalesced[j]].lower, 0, false};
+    std::vector<BelowBItem> items;
+    const std::string err = belowb_round_items(q.data(), coalesced, st, path, max_slice, items);
+    if (!err.empty()) return fail(P1HIP_ERR_HIP, err);
+    for (const BelowBLaunch& L : belowb_layout(items, ndev))
+      for (size_t it : L.items) {
+        device[coalesced[items[it].req]] = L.device;
+        tiles[coalesced[items[it].req]] = items[it].tiles;
+      }
+    return P1HIP_OK;
+  });
+}
+
+int p1hip_get_below_batch_stats(p1hip_below_batch_stats_t* out) {
+  if (!out) return fail(P1HIP_ERR_ARGS, "null stats pointer");
+  Runtime& R = rt();
+  std::lock_guard<std::mutex> g(R.mu);
+  *out = R.qstats;
+  return P1HIP_OK;
+}
+
+int p1hip_below_collect(const uint64_t* words, const uint32_t* req_tile0, const uint32_t* req_hit0, size_t nreq,
+                        uint32_t* idx, uint32_t* count) {
+  if (nreq == 0) return P1HIP_OK;
+  if (!req_tile0 || !req_hit0 || !count) return fail(P1HIP_ERR_ARGS, "null table or count array");
+  if (nreq > kBatchMaxTiles) return fail(P1HIP_ERR_ARGS, "too many requests");
+  // the kernel trusts its tables: every bound it relies on is checked here
+  if (req_tile0[0] != 0 || req_hit0[0] != 0) return fail(P1HIP_ERR_ARGS, "a request table does not start at 0");
+  for (size_t r = 0; r < nreq; ++r)
+    if (req_tile0[r + 1] < req_tile0[r] || req_hit0[r + 1] < req_hit0[r])
+      return fail(P1HIP_ERR_ARGS, "request " + std::to_string(r) + ": a request table falls");
+  if (req_tile0[nreq] > kBatchMaxTiles || req_hit0[nreq] > kBelowBatchMaxSlots)
+    return fail(P1HIP_ERR_ARGS, "more than 2^20 tiles or 2^22 slots");
+  if ((!words && req_tile0[nreq] > 0) || (!idx && req_hit0[nreq] > 0)) return fail(P1HIP_ERR_ARGS, "null words or idx array");
+  return guarded([&]() { return below_collect_locked(words, req_tile0, req_hit0, nreq, idx, count); });
 }
 
 int p1hip_scan_batch(const p1hip_request_t* reqs, size_t n, p1hip_result_t* out) {
@@ -2092,6 +2446,7 @@ void p1hip_reset_stats(void) {
   R.wstats = p1hip_wide_stats_t{};
   R.astats = p1hip_async_stats_t{};
   R.lstats = p1hip_below_stats_t{};
+  R.qstats = p1hip_below_batch_stats_t{};
   for (Dev& d : R.devs) {
     d.acc = p1hip_device_stats_t{};
     d.acc.shard_first = 1;  // empty until the next scan

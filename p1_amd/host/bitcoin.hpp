@@ -82,4 +82,21 @@ bitcoin::Message HandleRequest(const bitcoin::Message& req, uint64_t chunk = kDe
 std::vector<bitcoin::Message> HandleBatch(const std::vector<bitcoin::Message>& reqs, uint64_t chunk = kDefaultChunk,
                                           bool wide = false);
 
+
+// One target search: the nonces n of [lower, upper] with Hash(msg, n) <= target,
+// in increasing n, the first `cap` of them (p1hip_scan_below's question).
+struct BelowJob {
+  std::string msg;
+  uint64_t lower, upper, target, cap;
+};
+struct BelowHit {
+  uint64_t hash, nonce;
+};
+
+// Many target searches through one p1hip_scan_below_batch call: one list per
+// job, in order, each what p1hip_scan_below returns for it.  A cap above the
+// number of nonces in the job's range is asked for as that number (a range
+// cannot hold more hits); the caps of one call may add up to at most 2^26.
+std::vector<std::vector<BelowHit>> BelowBatch(const std::vector<BelowJob>& jobs);
+
 }  // namespace miner

@@ -4,6 +4,7 @@
 // the library; there is no CPU path.  HandleBatch answers many requests
 // through one p1hip_scan_batch (or p1hip_scan_batch_wide) call; AnswerPieces
 // is the backend of the multi-connection miner's rounds (miner_pool.hpp).
+// BelowBatch answers many target searches through one p1hip_scan_below_batch.
 #include <string>
 #include <vector>
 
@@ -77,6 +78,31 @@ std::vector<bitcoin::Message> HandleBatch(const std::vector<bitcoin::Message>& r
     throw bitcoin::HipError(rc, std::string(wide ? "p1hip_scan_batch_wide: " : "p1hip_scan_batch: ") + p1hip_last_error());
   for (size_t j = 0; j < idx.size(); ++j) res[idx[j]] = bitcoin::NewResult(out[j].hash, out[j].nonce);
   return res;
+}
+
+std::vector<std::vector<BelowHit>> BelowBatch(const std::vector<BelowJob>& jobs) {
+  std::vector<p1hip_below_request_t> q;
+  q.reserve(jobs.size());
+  size_t total = 0;
+  for (const BelowJob& j : jobs) {
+    uint64_t cap = j.cap;
+    if (j.lower > j.upper) cap = 0;
+    else if (j.upper - j.lower < cap) cap = j.upper - j.lower + 1;  // at most one hit per nonce
+    if (cap > (1ull << 26) || (total += (size_t)cap) > (1ull << 26))
+      throw bitcoin::HipError(P1HIP_ERR_ARGS, "below: the caps of one batch add up to more than 2^26 hits");
+    q.push_back({reinterpret_cast<const uint8_t*>(j.msg.data()), j.msg.size(), j.lower, j.upper, j.target, (size_t)cap});
+  }
+  std::vector<p1hip_result_t> hits(total);
+  std::vector<size_t> found(q.size(), 0);
+  const int rc = p1hip_scan_below_batch(q.data(), q.size(), hits.data(), hits.size(), found.data());
+  if (rc != P1HIP_OK) throw bitcoin::HipError(rc, std::string("p1hip_scan_below_batch: ") + p1hip_last_error());
+  std::vector<std::vector<BelowHit>> out(q.size());
+  size_t off = 0;
+  for (size_t i = 0; i < q.size(); ++i) {
+    for (size_t k = 0; k < found[i]; ++k) out[i].push_back({hits[off + k].hash, hits[off + k].nonce});
+    off += q[i].cap;
+  }
+  return out;
 }
 
 void AnswerPieces(const std::vector<Piece>& pieces, bool wide, std::vector<PieceResult>* out) {

@@ -42,6 +42,21 @@
 //                                        p1hip_scan_below: one "Result <hash>
 //                                        <nonce>" line per hit in nonce order;
 //                                        exits 0 with no line when there is none
+//   p1miner below [--device N] [--batch B]
+//                                        one target search per stdin line,
+//                                        "<msg-hex|-> <lower> <upper> <target>
+//                                        <cap>" ("-": the empty message); the
+//                                        lines are collected and answered
+//                                        together, in order, through one
+//                                        p1hip_scan_below_batch call, on the B-th
+//                                        line (default 256), on an empty line
+//                                        (itself not answered) or at EOF.  Every
+//                                        line is answered with "Hits <found>" and
+//                                        then <found> lines "Result <hash>
+//                                        <nonce>" in nonce order.  A line that
+//                                        does not parse ends the program with
+//                                        status 1 after the lines before it are
+//                                        answered.
 //   p1miner hash <msg> <nonce>           prints bitcoin.Hash(msg, nonce)
 //   p1miner serve [--device N] [--chunk C] [--batch B [--wide]]
 //                                        one JSON Message per stdin line; every
@@ -88,7 +103,8 @@
 
 static int usage() {
   fprintf(stderr,
-          "usage: p1miner scan <msg> <lower> <upper> [--below <target> [--count N]] | hash <msg> <nonce> | "
+          "usage: p1miner scan <msg> <lower> <upper> [--below <target> [--count N]] | below [--device N] [--batch B] | "
+          "hash <msg> <nonce> | "
           "serve [--device N] [--chunk C] [--batch B [--wide]] | lsp <host:port> [--device N] [--chunk C] [--epoch-limit K] "
           "[--epoch-millis M] [--window W] [--copies K] [--connect-copies K] "
           "[--conns C [--wide] [--linger-us U] [--round-log FILE] [--stats] [--inflight N]] | json | lsp-json | lsp-wrap <connID> <seq> | lsp-unwrap\n");
@@ -123,6 +139,81 @@ static int run_below(const char* msg, uint64_t lo, uint64_t hi, uint64_t target,
   }
   p1hip_shutdown();
   return 0;
+}
+
+// One line of `p1miner below`: "<msg-hex|-> <lower> <upper> <target> <cap>".
+static bool parse_below_line(const std::string& line, miner::BelowJob* job) {
+  std::vector<std::string> f;
+  size_t i = 0;
+  while (i < line.size()) {
+    while (i < line.size() && (line[i] == ' ' || line[i] == '\t' || line[i] == '\r')) ++i;
+    size_t j = i;
+    while (j < line.size() && line[j] != ' ' && line[j] != '\t' && line[j] != '\r') ++j;
+    if (j > i) f.push_back(line.substr(i, j - i));
+    i = j;
+  }
+  if (f.size() != 5) return false;
+  job->msg.clear();
+  if (f[0] != "-") {
+    if (f[0].size() % 2) return false;
+    for (size_t k = 0; k < f[0].size(); k += 2) {
+      int v = 0;
+      for (int d = 0; d < 2; ++d) {
+        const char c = f[0][k + d];
+        const int x = c >= '0' && c <= '9' ? c - '0' : c >= 'a' && c <= 'f' ? c - 'a' + 10 : c >= 'A' && c <= 'F' ? c - 'A' + 10 : -1;
+        if (x < 0) return false;
+        v = v * 16 + x;
+      }
+      job->msg.push_back((char)v);
+    }
+  }
+  return parse_u64(f[1].c_str(), &job->lower) && parse_u64(f[2].c_str(), &job->upper) &&
+         parse_u64(f[3].c_str(), &job->target) && parse_u64(f[4].c_str(), &job->cap);
+}
+
+// p1miner below: batches of target searches through miner::BelowBatch.  The
+// device is opened by the first batch that needs one (or, with --device, by
+// the first batch).
+static int run_below_batches(int dev, uint64_t batch) {
+  std::vector<miner::BelowJob> jobs;
+  bool opened = false;
+  auto flush = [&]() -> bool {
+    if (dev >= 0 && !opened) {
+      if (p1hip_init_devices(&dev, 1) != P1HIP_OK) {
+        fprintf(stderr, "p1hip init: %s\n", p1hip_last_error());
+        return false;
+      }
+      opened = true;
+    }
+    for (const std::vector<miner::BelowHit>& hits : miner::BelowBatch(jobs)) {
+      printf("Hits %zu\n", hits.size());
+      for (const miner::BelowHit& h : hits) printf("Result %" PRIu64 " %" PRIu64 "\n", h.hash, h.nonce);
+    }
+    fflush(stdout);
+    jobs.clear();
+    return true;
+  };
+  std::string line;
+  uint64_t lineno = 0;
+  int rc = 0;
+  while (std::getline(std::cin, line)) {
+    ++lineno;
+    if (line.empty()) {  // flush now; the empty line itself is not answered
+      if (!jobs.empty() && !flush()) return 1;
+      continue;
+    }
+    miner::BelowJob job;
+    if (!parse_below_line(line, &job)) {
+      fprintf(stderr, "below: line %" PRIu64 " is not \"<msg-hex|-> <lower> <upper> <target> <cap>\"\n", lineno);
+      rc = 1;
+      break;
+    }
+    jobs.push_back(job);
+    if (jobs.size() >= batch && !flush()) return 1;
+  }
+  if (!jobs.empty() && !flush()) return 1;
+  p1hip_shutdown();
+  return rc;
 }
 
 // p1miner lsp --conns C: the GPU is open; run the pool (miner_pool.hpp) over
@@ -244,6 +335,16 @@ int main(int argc, char** argv) {
       }
       if (!below) return usage();  // --count means nothing to the minimum scan
       return run_below(argv[2], lo, hi, target, count);
+    }
+    if (cmd == "below") {
+      int dev = -1;
+      uint64_t batch = 256, d = 0;
+      for (int i = 2; i < argc; ++i) {
+        if (!strcmp(argv[i], "--device") && i + 1 < argc) { if (!parse_u64(argv[++i], &d) || d > 1023) return usage(); dev = (int)d; }
+        else if (!strcmp(argv[i], "--batch") && i + 1 < argc) { if (!parse_u64(argv[++i], &batch) || batch == 0) return usage(); }
+        else return usage();
+      }
+      return run_below_batches(dev, batch);
     }
     if (cmd == "hash" && argc == 4) {
       uint64_t n;

@@ -1,5 +1,5 @@
-// batch_emu -- TEST TOOL: replays a p1hip_scan_batch or p1hip_scan_batch_wide
-// call on the host.
+// batch_emu -- TEST TOOL: replays a p1hip_scan_batch, p1hip_scan_batch_wide or
+// p1hip_scan_below_batch call on the host.
 //
 // It lays the requests out with the library's own batch_layout, builds every
 // launch pair's tables with the library's own batch_build_table
@@ -29,6 +29,20 @@
 //   exactly once and every range must lie inside the array.
 //   stderr: "launches=<k_scan launches> tiles=<n> segs=<k_scan segments> gsegs=<n> ranges=<n> small=<n> wide=<n>"
 //   a request above 2^24 nonces is refused: exit status 1
+//
+// usage: batch_emu below <ndev> [maxslice=N] [corrupt=K] < requests
+//   replays p1hip_scan_below_batch with the library's own belowb_plan.hpp:
+//   routes, rounds, the layout of every round with its tile and slot caps and
+//   the tables; per launch pair k_belowb_mark (below_thread per simulated
+//   thread against the request's own target, one word per wave),
+//   k_belowb_collect (belowb_collect_replay: the shared word expansion) and
+//   the library's decoder.  maxslice=N is P1HIP_BELOW_MAX_SLICE.  corrupt=K
+//   adds 1 to the K-th index the first launch pair returns before it is
+//   decoded (the decoder must refuse it: exit status 1).
+//   stdin: one request per line, "<msg-hex|-> <lower> <upper> <target> <cap>"
+//   stdout: per request one line, "<found>" and then " <hash>:<nonce>" per hit
+//   stderr: "rounds=<n> launches=<n> tiles=<n> slots=<n> coalesced=<n> empty=<n>"
+//   a request on the individual route is refused: exit status 1
 #include <inttypes.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -39,6 +53,7 @@
 #include <thread>
 #include <vector>
 
+#include "../p1_amd/csrc/belowb_plan.hpp"
 #include "../p1_amd/csrc/wide_plan.hpp"
 #include "scan_replay.hpp"
 
@@ -232,7 +247,130 @@ static int replay_wide(const std::vector<BatchReq>& reqs, int ndev, uint32_t max
   return 0;
 }
 
+// The p1hip_scan_below_batch replay.
+static int replay_below(const std::vector<BelowBReq>& reqs, int ndev, uint64_t max_slice, long corrupt) {
+  const size_t n = reqs.size();
+  std::vector<size_t> coalesced;
+  uint64_t empty = 0;
+  for (size_t i = 0; i < n; ++i) {
+    const int route = belowb_route(reqs[i], kBelowAuto, max_slice);
+    if (route == kBelowBIndividual) {
+      fprintf(stderr, "request %zu takes the individual route: not a below batch replay\n", i);
+      return 1;
+    }
+    if (route == kBelowBCoalesced) coalesced.push_back(i);
+    else empty++;
+  }
+  std::vector<std::vector<Key>> res(n);
+  std::vector<BelowBState> st(coalesced.size());
+  for (size_t j = 0; j < coalesced.size(); ++j) st[j] = {reqs[coalesced[j]].lower, 0, false};
+  uint64_t rounds = 0, nlaunch = 0, tiles = 0, slots = 0;
+  std::vector<BelowBItem> items;
+  BelowBTable B;
+  std::vector<std::vector<Key>> got;
+  const uint64_t unwritten = 0x756e7772697474ull;  // every word must be overwritten
+  for (size_t left = coalesced.size(); left > 0; ++rounds) {
+    std::string err = belowb_round_items(reqs.data(), coalesced, st, kBelowAuto, max_slice, items);
+    if (!err.empty()) {
+      fprintf(stderr, "round error: %s\n", err.c_str());
+      return 1;
+    }
+    for (const BelowBLaunch& L : belowb_layout(items, ndev)) {
+      err = belowb_build_table(reqs.data(), coalesced, items, L, B);
+      if (!err.empty()) {
+        fprintf(stderr, "table error: %s\n", err.c_str());
+        return 1;
+      }
+      if (L.tiles > kBatchMaxTiles || L.slots > kBelowBatchMaxSlots) {
+        fprintf(stderr, "launch pair of %u tiles, %llu slots\n", L.tiles, (unsigned long long)L.slots);
+        return 1;
+      }
+      const size_t nreq = L.items.size();
+      // k_belowb_mark: grid = L.tiles workgroups of kBlock threads, one word per wave
+      std::vector<uint64_t> marks((size_t)L.tiles * kBelowWordsPerTile, unwritten);
+      for_tiles(L.tiles, [&](uint32_t b) {
+        const BatchSeg& S = B.T.segs[batch_find_seg(B.T.segs.data(), (uint32_t)B.T.segs.size(), b)];
+        const uint64_t target = B.targets[S.req];
+        for (uint32_t w = 0; w < kBelowWordsPerTile; ++w) {
+          uint64_t word = 0;
+          for (uint32_t l = 0; l < 64; ++l)
+            if (below_thread(S.ga, (uint64_t)(b - S.block0) * kBlock + w * 64u + l, target)) word |= 1ull << l;
+          marks[(size_t)b * kBelowWordsPerTile + w] = word;
+        }
+      });
+      // k_belowb_collect: grid = requests of the launch pair
+      std::vector<uint32_t> idx((size_t)L.slots + 1, ~0u), count(nreq, ~0u);
+      for (uint32_t r = 0; r < (uint32_t)nreq; ++r)
+        belowb_collect_replay(marks.data(), B.T.req_tile0.data(), B.req_hit0.data(), r, idx.data(), count.data());
+      if (idx[L.slots] != ~0u) {
+        fprintf(stderr, "an index past the launch pair's slots was written\n");
+        return 1;
+      }
+      if (corrupt >= 0 && nlaunch == 0 && (uint64_t)corrupt < L.slots) idx[(size_t)corrupt] += 1;
+      err = belowb_decode(B, idx.data(), count.data(), got);
+      if (!err.empty()) {
+        fprintf(stderr, "decode error: %s\n", err.c_str());
+        return 1;
+      }
+      for (size_t r = 0; r < nreq; ++r) {
+        const BelowBItem& it = items[L.items[r]];
+        BelowBState& S = st[it.req];
+        const size_t i = coalesced[it.req];
+        for (const Key& k : got[r]) res[i].push_back(k);
+        S.found += got[r].size();
+        if (S.found == reqs[i].cap || it.hi == reqs[i].upper) {
+          S.done = true;
+          --left;
+        } else {
+          S.lo = it.hi + 1;
+        }
+      }
+      nlaunch++;
+      tiles += L.tiles;
+      slots += L.slots;
+    }
+  }
+  for (size_t i = 0; i < n; ++i) {
+    printf("%zu", res[i].size());
+    for (const Key& k : res[i]) printf(" %" PRIu64 ":%" PRIu64, k.h, k.n);
+    printf("\n");
+  }
+  fprintf(stderr, "rounds=%" PRIu64 " launches=%" PRIu64 " tiles=%" PRIu64 " slots=%" PRIu64 " coalesced=%zu empty=%" PRIu64 "\n",
+          rounds, nlaunch, tiles, slots, coalesced.size(), empty);
+  return 0;
+}
+
+static int main_below(int argc, char** argv) {
+  const int ndev = argc > 2 ? atoi(argv[2]) : 0;
+  uint64_t max_slice = 0;
+  long corrupt = -1;
+  bool bad = ndev < 1;
+  for (int i = 3; i < argc; ++i) {
+    if (!strncmp(argv[i], "maxslice=", 9)) max_slice = strtoull(argv[i] + 9, nullptr, 10);
+    else if (!strncmp(argv[i], "corrupt=", 8)) corrupt = atol(argv[i] + 8);
+    else bad = true;
+  }
+  if (bad) {
+    fprintf(stderr, "usage: %s below <ndev> [maxslice=N] [corrupt=K] < requests\n", argv[0]);
+    return 2;
+  }
+  std::vector<std::vector<uint8_t>> msgs;
+  std::vector<BelowBReq> reqs;
+  char hex[4096];
+  uint64_t a, b, t, c;
+  while (scanf("%4095s %" SCNu64 " %" SCNu64 " %" SCNu64 " %" SCNu64, hex, &a, &b, &t, &c) == 5) {
+    msgs.push_back(strcmp(hex, "-") == 0 ? std::vector<uint8_t>() : unhex(hex));
+    reqs.push_back({nullptr, 0, a, b, t, c});
+  }
+  for (size_t i = 0; i < reqs.size(); ++i) {
+    reqs[i].msg = msgs[i].data();
+    reqs[i].len = msgs[i].size();
+  }
+  return replay_below(reqs, ndev, max_slice, corrupt);
+}
+
 int main(int argc, char** argv) {
+  if (argc > 1 && strcmp(argv[1], "below") == 0) return main_below(argc, argv);
   const bool wide = argc > 1 && strcmp(argv[1], "wide") == 0;
   const int a0 = wide ? 2 : 1;
   const int ndev = argc > a0 ? atoi(argv[a0]) : 1;
