@@ -5,7 +5,7 @@ HIPFLAGS ?= -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -Wall
 LLVM ?= /opt/rocm/lib/llvm/bin
 CSRC := p1_amd/csrc
 HDRS := $(CSRC)/sha256_dev.hpp $(CSRC)/scan_core.hpp $(CSRC)/planner.hpp $(CSRC)/fast_variants.inc $(CSRC)/variant_cost.inc \
-        $(CSRC)/scan_abi.hpp $(CSRC)/scan_pack.hpp $(CSRC)/tile_map.hpp $(CSRC)/argmin_dev.hpp $(CSRC)/batch_abi.hpp $(CSRC)/batch_plan.hpp $(CSRC)/wide_plan.hpp $(CSRC)/async_slots.hpp $(CSRC)/below_abi.hpp $(CSRC)/below_plan.hpp $(CSRC)/belowb_abi.hpp $(CSRC)/belowb_plan.hpp include/p1hip.h
+        $(CSRC)/scan_abi.hpp $(CSRC)/scan_pack.hpp $(CSRC)/tile_map.hpp $(CSRC)/argmin_dev.hpp $(CSRC)/batch_abi.hpp $(CSRC)/batch_plan.hpp $(CSRC)/wide_plan.hpp $(CSRC)/async_slots.hpp $(CSRC)/below_abi.hpp $(CSRC)/below_plan.hpp $(CSRC)/belowb_abi.hpp $(CSRC)/belowb_plan.hpp $(CSRC)/beloww_abi.hpp $(CSRC)/beloww_plan.hpp include/p1hip.h
 # what the device code includes (the host-side planner does not rebuild it)
 DEVHDRS := $(CSRC)/sha256_dev.hpp $(CSRC)/scan_core.hpp $(CSRC)/fast_variants.inc $(CSRC)/scan_abi.hpp $(CSRC)/argmin_dev.hpp
 # device code: HIP C++ -> gfx950 assembly -> tools/isa_post.py post-pass
@@ -121,7 +121,31 @@ isa-belowb:
 	mkdir -p $(BUILD)
 	$(HIPCC) $(BELOWBDEVFLAGS) -c -o /dev/null $(CSRC)/p1hip_belowb_kernels.hip -Rpass-analysis=kernel-resource-usage 2> $(BUILD)/resource_belowb.txt || true
 
-BLOBS := $(BUILD)/p1hip_kernels_blob.o $(BUILD)/p1hip_batch_blob.o $(BUILD)/p1hip_below_blob.o $(BUILD)/p1hip_belowb_blob.o
+# The filter kernel of p1hip_scan_below_batch_wide (k_beloww_filter): a fifth
+# code object of its own, built as the third and fourth are, so the other four
+# stay byte-identical.  Its blob is linked after them.
+BELOWWDEVHDRS := $(CSRC)/scan_abi.hpp $(CSRC)/batch_abi.hpp $(CSRC)/beloww_abi.hpp
+BELOWWDEVFLAGS ?= -O3 -std=c++17 --offload-arch=$(ARCH) --cuda-device-only -Wall
+.SECONDARY: $(BUILD)/p1hip_beloww.s $(BUILD)/p1hip_beloww.o
+$(BUILD)/p1hip_beloww.s: $(CSRC)/p1hip_beloww_kernels.hip $(BELOWWDEVHDRS)
+	mkdir -p $(BUILD)
+	$(HIPCC) $(BELOWWDEVFLAGS) -S -o $@ $(CSRC)/p1hip_beloww_kernels.hip
+
+$(BUILD)/p1hip_beloww.o: $(BUILD)/p1hip_beloww.s
+	$(LLVM)/clang -cc1as -triple amdgcn-amd-amdhsa -filetype obj -target-cpu $(ARCH) -mrelocation-model pic -o $@ $<
+
+$(BUILD)/p1hip_beloww.hsaco: $(BUILD)/p1hip_beloww.o
+	$(LLVM)/ld.lld -m elf64_amdgpu --no-undefined -shared -o $@ $<
+
+$(BUILD)/p1hip_beloww_blob.o: $(CSRC)/p1hip_beloww_blob.S $(BUILD)/p1hip_beloww.hsaco
+	gcc -c -fPIC -DP1HIP_BELOWW_CO='"$(CURDIR)/$(BUILD)/p1hip_beloww.hsaco"' -o $@ $<
+
+# resource report of the filter kernel (registers, scratch: it must not spill)
+isa-beloww:
+	mkdir -p $(BUILD)
+	$(HIPCC) $(BELOWWDEVFLAGS) -c -o /dev/null $(CSRC)/p1hip_beloww_kernels.hip -Rpass-analysis=kernel-resource-usage 2> $(BUILD)/resource_beloww.txt || true
+
+BLOBS := $(BUILD)/p1hip_kernels_blob.o $(BUILD)/p1hip_batch_blob.o $(BUILD)/p1hip_below_blob.o $(BUILD)/p1hip_belowb_blob.o $(BUILD)/p1hip_beloww_blob.o
 
 $(BUILD)/p1hip_host.o: $(CSRC)/p1hip.hip $(HDRS)
 	mkdir -p $(BUILD)
@@ -232,7 +256,9 @@ tools/p1emu: tools/p1emu.cpp tools/scan_replay.hpp $(HDRS)
 # host-only replay of a p1hip_scan_batch call: the library's own table builder
 # and segment lookup, generic_thread per thread, the per-request fold;
 # (`batch_emu below`) of a p1hip_scan_below_batch call: the library's own
-# belowb_plan.hpp, below_thread per thread, the shared word expansion; and
+# belowb_plan.hpp, below_thread per thread, the shared word expansion;
+# (`batch_emu beloww`) of a p1hip_scan_below_batch_wide call: the library's own
+# beloww_plan.hpp, k_scan tile by tile, the shared filter restatement; and
 # (`batch_emu wide`) of a p1hip_scan_batch_wide call: the library's own
 # wide_plan.hpp, k_scan tile by tile, the range fold
 tools/batch_emu: tools/batch_emu.cpp tools/scan_replay.hpp $(HDRS)
@@ -361,9 +387,9 @@ $(SANDIR)/fuzz_codecs: tests/fuzz/fuzz_codecs.cpp p1_amd/host/bitcoin.cpp p1_amd
 #   make variant NAME=x DEVEXTRA='-DP1_FAST_WAVES=5' ISAPOST='--no-e64'
 #   make variant NAME=nv2 DEVEXTRA=-DP1_NV2_PLAIN HOSTEXTRA=-DP1_NV2_PLAIN   (+ P1HIP_NO_SPLIT=1 at run time)
 variant:
-	$(MAKE) BUILD=build/var_$(NAME) DEVEXTRA="$(DEVEXTRA)" HIPFLAGS="$(HIPFLAGS) $(HOSTEXTRA)" ISAPOST="$(ISAPOST)" build/var_$(NAME)/p1hip_kernels_blob.o build/var_$(NAME)/p1hip_batch_blob.o build/var_$(NAME)/p1hip_below_blob.o build/var_$(NAME)/p1hip_belowb_blob.o build/var_$(NAME)/p1hip_host.o
+	$(MAKE) BUILD=build/var_$(NAME) DEVEXTRA="$(DEVEXTRA)" HIPFLAGS="$(HIPFLAGS) $(HOSTEXTRA)" ISAPOST="$(ISAPOST)" build/var_$(NAME)/p1hip_kernels_blob.o build/var_$(NAME)/p1hip_batch_blob.o build/var_$(NAME)/p1hip_below_blob.o build/var_$(NAME)/p1hip_belowb_blob.o build/var_$(NAME)/p1hip_beloww_blob.o build/var_$(NAME)/p1hip_host.o
 	mkdir -p p1_amd/variants
-	$(HIPCC) -shared -fPIC -o p1_amd/variants/libp1hip_$(NAME).so build/var_$(NAME)/p1hip_host.o build/var_$(NAME)/p1hip_kernels_blob.o build/var_$(NAME)/p1hip_batch_blob.o build/var_$(NAME)/p1hip_below_blob.o build/var_$(NAME)/p1hip_belowb_blob.o -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
+	$(HIPCC) -shared -fPIC -o p1_amd/variants/libp1hip_$(NAME).so build/var_$(NAME)/p1hip_host.o build/var_$(NAME)/p1hip_kernels_blob.o build/var_$(NAME)/p1hip_batch_blob.o build/var_$(NAME)/p1hip_below_blob.o build/var_$(NAME)/p1hip_belowb_blob.o build/var_$(NAME)/p1hip_beloww_blob.o -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
 
 # ISA + resource report of the scan kernels (for DESIGN.md / profiling):
 # build/p1hip_kernels.post.s is the exact assembly that ships
@@ -374,6 +400,6 @@ clean:
 	rm -f p1_amd/libp1hip.so tools/libp1clock.so tools/queue_ctl tools/p1emu tools/batch_emu p1_amd/p1miner p1_amd/p1server p1_amd/p1client tools/lsp_scenarios tools/lsp_fake_miner tools/lsp_fake_pool tools/pool_test tools/lsp_load tools/wcal tools/vbank \
 	    tools/async_slots_test tools/pool_pipeline_test tools/lsp_fake_pool_async p1_amd/p1gpuserver tools/lsp_fake_server_local \
     tools/local_slots_test tools/lsp_jobs
-	rm -rf $(BUILD)/p1hip_kernels* $(BUILD)/p1hip_batch* $(BUILD)/p1hip_below_* $(BUILD)/p1hip_below.* $(BUILD)/p1hip_belowb* $(BUILD)/p1hip_host.o
+	rm -rf $(BUILD)/p1hip_kernels* $(BUILD)/p1hip_batch* $(BUILD)/p1hip_below_* $(BUILD)/p1hip_below.* $(BUILD)/p1hip_belowb* $(BUILD)/p1hip_beloww* $(BUILD)/p1hip_host.o
 	$(MAKE) -C oracle clean
-.PHONY: all oracle clean isa isa-below isa-belowb variant sanitize sanitize-emu sanitize-lib sanitize-lib-tsan fuzz
+.PHONY: all oracle clean isa isa-below isa-belowb isa-beloww variant sanitize sanitize-emu sanitize-lib sanitize-lib-tsan fuzz

@@ -456,6 +456,122 @@ int p1hip_get_below_batch_stats(p1hip_below_batch_stats_t *out);   /* cleared by
 int p1hip_below_collect(const uint64_t *words, const uint32_t *req_tile0, const uint32_t *req_hit0,
                         size_t nreq, uint32_t *idx, uint32_t *count);
 
+/* Hard-target searches share k_scan.  p1hip_scan_below_batch coalesces only
+ * requests whose first slice is dense; a request with a hard target -- a pool's
+ * share target, a server's "first nonce at or below T" over a chunk of 2^24
+ * nonces -- has a sparse first slice of 2^16..2^24 nonces and would run alone:
+ * a k_scan launch of a few dozen workgroups, a copy back of every partial, a
+ * host filter, a mark launch, two synchronisations.  Here the sparse slices of
+ * all such requests share k_scan launches exactly as the wide requests of
+ * p1hip_scan_batch_wide do, k_beloww_filter (a fifth code object) turns each
+ * request's partials into its candidate tiles on the device, and one
+ * k_belowb_mark launch per device refines all candidates of all its requests.
+ *
+ * The contract is p1hip_scan_below_batch's, word for word: request i owns
+ * hits[off_i .. off_i + cap_i), off_i = the sum of the caps before it (computed
+ * with an overflow check; above hits_len: P1HIP_ERR_ARGS); found[i] entries of
+ * it are written and they are exactly what p1hip_scan_below(reqs[i]...)
+ * returns; every request is validated before anything runs (P1HIP_ERR_ARGS
+ * names the index); `hits` and `found` are untouched on any error; n == 0 and
+ * a call whose requests are all empty open no device; synchronous under the
+ * library's lock; legal while tickets are outstanding.  Routes, rounds, groups
+ * and device count never show in the result.
+ *
+ * Routes, fixed from the first slice (p1hip_below_wide_layout reports them):
+ *   0 empty: lower > upper or cap == 0
+ *   1 coalesced: the first slice is dense and has at most
+ *     P1HIP_BELOW_BATCH_MAX_NONCES nonces: p1hip_scan_below_batch's route and
+ *     machinery
+ *   3 filtered: the first slice is sparse and has at most
+ *     P1HIP_BELOW_WIDE_MAX_NONCES nonces
+ *   2 individual: every other request, one by one through p1hip_scan_below's
+ *     own path after the rounds; these count in p1hip_below_stats_t as calls
+ * A later slice is never longer than the first; a filtered request's later
+ * slice is sparse, or has fallen to at most 2^16 nonces and become dense, and
+ * then it goes through the dense launch pair of the same round; a coalesced
+ * request never turns sparse.
+ *
+ * A round takes the next slice of every unfinished coalesced and filtered
+ * request.  The dense slices go into launch pairs as in p1hip_scan_below_batch.
+ * The sparse ones run in groups (one, unless a device's partial array of 2^24
+ * tiles is full: the slices turned away form a further group of the round).
+ * Phase A of a group, every device enqueued before any is synchronised: the
+ * shared k_scan launches, one k_batch_scan for the ragged edges, then
+ * k_beloww_filter, one workgroup per request, which writes the indices of the
+ * request's first `slots` candidate tiles (partial at or below the target) and
+ * the number of all of them; one count per request and its slots are copied
+ * back.  slots = min(tiles, 16 + 4 * ceil(len * (target + 1) / 2^64)): four
+ * times the expected hits of the slice plus 16.  A request that reports more
+ * candidates than slots is still answered exactly: the host copies that
+ * request's partials back and filters them itself (slot_overflows).  Phase B:
+ * the host turns every candidate into its tile's nonces, k_belowb_mark marks
+ * them on the request's own device against the request's own target, and the
+ * marks are copied back and decoded.
+ * Checks kept in the product, a failure of any is P1HIP_ERR_HIP: every
+ * candidate index lies in its request's ranges, in table order; its partial is
+ * at or below the target; every marked thread is a nonce of its piece and its
+ * hash, recomputed on the host, is at or below the target; each candidate
+ * tile's refinement has exactly the tile's partial as its minimum; a request's
+ * nonces are strictly increasing across rounds; and p1hip_scan_below_batch's
+ * own checks for the dense slices. */
+#define P1HIP_BELOW_WIDE_MAX_NONCES ((uint64_t)1 << 24)
+int p1hip_scan_below_batch_wide(const p1hip_below_request_t *reqs, size_t n,
+                                p1hip_result_t *hits, size_t hits_len, size_t *found /* n */);
+
+/* Host only (no device): the routes of a call and the layout of its first
+ * round (first group) over ndev devices.  route[i]: as above; device[i]: the
+ * device of a coalesced or filtered request's first slice (-1 otherwise; -1
+ * also for a filtered slice deferred to a further group); tiles[i]: that
+ * slice's workgroup tiles (0 otherwise); slots[i]: a coalesced slice's hit
+ * slots, a filtered slice's candidate slots (0 otherwise). */
+int p1hip_below_wide_layout(const p1hip_below_request_t *reqs, size_t n, int ndev,
+                            int32_t *route, int32_t *device, uint32_t *tiles, uint32_t *slots);
+
+/* Accounting of p1hip_scan_below_batch_wide since p1hip_reset_stats.
+ * Individual requests also count in p1hip_below_stats_t as calls; the k_scan
+ * launches also count in each device's p1hip_device_stats_t.
+ * p1hip_below_batch_stats_t is not touched. */
+typedef struct {
+  uint64_t calls;            /* p1hip_scan_below_batch_wide calls that succeeded  */
+  uint64_t requests;         /* requests in them                                  */
+  uint64_t empty;            /* ... per route: lower > upper or cap == 0          */
+  uint64_t coalesced;        /*     dense, sharing launch pairs                   */
+  uint64_t filtered;         /*     sparse, sharing k_scan launches               */
+  uint64_t individual;       /*     run one by one                                */
+  uint64_t rounds;           /* rounds of the coalesced and filtered routes       */
+  uint64_t groups;           /* groups of sparse slices (wide_layout calls)       */
+  uint64_t scan_launches;    /* shared k_scan launches                            */
+  uint64_t scan_segments;    /* segments in them                                  */
+  uint64_t generic_launches; /* k_batch_scan launches (ragged edges)              */
+  uint64_t scan_nonces;      /* nonces of the sparse slices (both kernels)        */
+  uint64_t filter_launches;  /* k_beloww_filter launches                          */
+  uint64_t candidate_tiles;  /* tiles with a partial <= target and a valid thread */
+  uint64_t slot_overflows;   /* requests of a round with more candidates than
+                                slots, answered by the host filter               */
+  uint64_t mark_launches;    /* k_belowb_mark launches (dense pairs and phase B)  */
+  uint64_t mark_tiles;       /* workgroups of those launches                      */
+  uint64_t mark_nonces;      /* nonces they hashed                                */
+  uint64_t hits;             /* hits returned (all routes)                        */
+  uint64_t bytes_back;       /* bytes copied back from the devices (rounds)       */
+  double wall_ms;            /* host wall time inside the call                    */
+} p1hip_below_wide_stats_t;
+int p1hip_get_below_wide_stats(p1hip_below_wide_stats_t *out);   /* cleared by p1hip_reset_stats */
+
+/* Test hook: k_beloww_filter alone, on the first device, over a crafted partial
+ * array of ntiles (hash, nonce) pairs.  Request r of nreq owns the ranges
+ * [range_tile0[j], range_tile0[j] + range_ntiles[j]) for j in
+ * [req_range0[r], req_range0[r + 1]) and slots [req_slot0[r], req_slot0[r + 1])
+ * of `cand` (both request tables have nreq + 1 entries, start at 0 and never
+ * fall; every range lies inside the array; at most 2^24 tiles, 2^24 slots and
+ * 2^24 ranges).  cand receives, per request, the partial-array indices of its
+ * first tiles with hash <= targets[r], in table order, as many as it has
+ * slots; count[r] the number of all such tiles, not clamped; slots the kernel
+ * does not write read UINT32_MAX.  Counts in no statistics. */
+int p1hip_below_filter(const uint64_t *part_hash, const uint64_t *part_nonce, size_t ntiles,
+                       const uint32_t *range_tile0, const uint32_t *range_ntiles,
+                       const uint32_t *req_range0, const uint64_t *targets, const uint32_t *req_slot0,
+                       size_t nreq, uint32_t *cand, uint32_t *count);
+
 /* Kernel-level accounting.  One p1hip_scan = one (rarely several) launch of
  * the scan kernel k_scan per device, covering every decade of the range; a
  * share of at most 2^16 nonces is one launch of k_scan_small instead (plan in
@@ -550,7 +666,9 @@ int p1hip_comm_info(int index, int *nranks, int *rank);
  * p1hip_below_stats_t and the P1HIP_BELOW_* constants, and with
  * p1hip_scan_below_batch, p1hip_below_batch_layout,
  * p1hip_get_below_batch_stats, the test hook p1hip_below_collect and their
- * structs: purely additive, the layout of every existing struct is
+ * structs, and with p1hip_scan_below_batch_wide, p1hip_below_wide_layout,
+ * p1hip_get_below_wide_stats, p1hip_below_wide_stats_t and the test hook
+ * p1hip_below_filter: purely additive, the layout of every existing struct is
  * unchanged. */
 #define P1HIP_ABI_VERSION 6
 int p1hip_abi_version(void);

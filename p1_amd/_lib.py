@@ -167,6 +167,35 @@ class BelowBatchStats(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class BelowWideStats(ctypes.Structure):
+    _fields_ = [
+        ("calls", U64),
+        ("requests", U64),
+        ("empty", U64),
+        ("coalesced", U64),
+        ("filtered", U64),
+        ("individual", U64),
+        ("rounds", U64),
+        ("groups", U64),
+        ("scan_launches", U64),
+        ("scan_segments", U64),
+        ("generic_launches", U64),
+        ("scan_nonces", U64),
+        ("filter_launches", U64),
+        ("candidate_tiles", U64),
+        ("slot_overflows", U64),
+        ("mark_launches", U64),
+        ("mark_tiles", U64),
+        ("mark_nonces", U64),
+        ("hits", U64),
+        ("bytes_back", U64),
+        ("wall_ms", ctypes.c_double),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class DeviceInfo(ctypes.Structure):
     _fields_ = [
         ("ordinal", ctypes.c_int32),
@@ -247,6 +276,18 @@ SIGNATURES = [
     ("p1hip_below_collect", ctypes.c_int,
      [ctypes.POINTER(U64), ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32), ctypes.c_size_t,
       ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]),
+    ("p1hip_scan_below_batch_wide", ctypes.c_int,
+     [ctypes.POINTER(BelowRequest), ctypes.c_size_t, ctypes.POINTER(Result), ctypes.c_size_t,
+      ctypes.POINTER(ctypes.c_size_t)]),
+    ("p1hip_below_wide_layout", ctypes.c_int,
+     [ctypes.POINTER(BelowRequest), ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(ctypes.c_int32),
+      ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]),
+    ("p1hip_get_below_wide_stats", ctypes.c_int, [ctypes.POINTER(BelowWideStats)]),
+    ("p1hip_below_filter", ctypes.c_int,
+     [ctypes.POINTER(U64), ctypes.POINTER(U64), ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint32),
+      ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(U64),
+      ctypes.POINTER(ctypes.c_uint32), ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint32),
+      ctypes.POINTER(ctypes.c_uint32)]),
     ("p1hip_hash", ctypes.c_int, [ctypes.c_char_p, ctypes.c_size_t, U64, ctypes.POINTER(U64)]),
     ("p1hip_plan_shards", ctypes.c_int,
      [ctypes.c_char_p, ctypes.c_size_t, U64, U64, ctypes.c_int, ctypes.POINTER(U64), ctypes.POINTER(U64)]),
@@ -549,6 +590,86 @@ def belowb_codeobj_sha256(lib=None):
     end = ctypes.addressof(ctypes.c_char.in_dll(lib, "p1hip_belowb_co_end"))
     if end <= start:
         raise P1HipError(-100, "embedded below batch code object is empty")
+    return hashlib.sha256(ctypes.string_at(start, end - start)).hexdigest()
+
+
+# include/p1hip.h P1HIP_BELOW_WIDE_MAX_NONCES; route[i] of p1hip_below_wide_layout
+BELOW_WIDE_MAX_NONCES = 1 << 24
+BELOW_WIDE_ROUTES = ("empty", "coalesced", "individual", "filtered")
+
+
+def scan_below_batch_wide(requests):
+    """p1hip_scan_below_batch_wide: scan_below_batch's contract and result;
+    the requests whose first slice is sparse and of at most 2^24 nonces (hard
+    targets) share k_scan launches and a filter kernel instead of running one
+    by one."""
+    arr, rows = _below_requests(requests)
+    n = len(rows)
+    total = sum(r[4] for r in rows)
+    hits = (Result * max(total, 1))()
+    found = (ctypes.c_size_t * max(n, 1))()
+    _check(load().p1hip_scan_below_batch_wide(arr, n, hits, total, found))
+    out, off = [], 0
+    for i in range(n):
+        out.append([(hits[off + k].hash, hits[off + k].nonce) for k in range(found[i])])
+        off += rows[i][4]
+    return out
+
+
+def below_wide_layout(requests, ndev):
+    """p1hip_below_wide_layout: per request {"route" (one of BELOW_WIDE_ROUTES),
+    "device", "tiles", "slots"} of scan_below_batch_wide's first round over
+    `ndev` devices (device -1, tiles and slots 0 unless coalesced or filtered).
+    Host-only."""
+    arr, rows = _below_requests(requests)
+    n = len(rows)
+    route, device = (ctypes.c_int32 * max(n, 1))(), (ctypes.c_int32 * max(n, 1))()
+    tiles, slots = (ctypes.c_uint32 * max(n, 1))(), (ctypes.c_uint32 * max(n, 1))()
+    _check(load().p1hip_below_wide_layout(arr, n, int(ndev), route, device, tiles, slots))
+    return [{"route": BELOW_WIDE_ROUTES[route[i]], "device": device[i], "tiles": tiles[i], "slots": slots[i]}
+            for i in range(n)]
+
+
+def get_below_wide_stats():
+    """Accounting of scan_below_batch_wide since reset_stats (p1hip_get_below_wide_stats)."""
+    s = BelowWideStats()
+    _check(load().p1hip_get_below_wide_stats(ctypes.byref(s)))
+    return s.as_dict()
+
+
+def below_filter(part, ranges, req_range0, targets, req_slot0):
+    """p1hip_below_filter (test hook): k_beloww_filter alone over the partial
+    array `part` [(hash, nonce)]; `ranges` is [(tile0, ntiles)], request r owns
+    ranges [req_range0[r], req_range0[r + 1]) and slots [req_slot0[r],
+    req_slot0[r + 1]).  Returns (cand, count): every slot (UINT32_MAX where
+    the kernel wrote nothing) and the candidates of each request, not clamped."""
+    nreq = len(req_range0) - 1
+    assert nreq >= 0 and len(req_slot0) == nreq + 1 and len(targets) == nreq and len(ranges) == req_range0[-1]
+    nt = len(part)
+    ha = (U64 * max(nt, 1))(*[h for h, _ in part])
+    na = (U64 * max(nt, 1))(*[x for _, x in part])
+    t0 = (ctypes.c_uint32 * max(len(ranges), 1))(*[a for a, _ in ranges])
+    tn = (ctypes.c_uint32 * max(len(ranges), 1))(*[b for _, b in ranges])
+    ra = (ctypes.c_uint32 * (nreq + 1))(*req_range0)
+    sa = (ctypes.c_uint32 * (nreq + 1))(*req_slot0)
+    ta = (U64 * max(nreq, 1))(*targets)
+    cand = (ctypes.c_uint32 * max(req_slot0[-1], 1))()
+    count = (ctypes.c_uint32 * max(nreq, 1))()
+    _check(load().p1hip_below_filter(ha, na, nt, t0, tn, ra, ta, sa, nreq, cand, count))
+    return list(cand[:req_slot0[-1]]), list(count[:nreq])
+
+
+def beloww_codeobj_sha256(lib=None):
+    """sha256 (hex) of the fifth embedded code object, the filter kernel of
+    scan_below_batch_wide (p1hip_beloww_co .. p1hip_beloww_co_end of
+    csrc/p1hip_beloww_blob.S)."""
+    import hashlib
+
+    lib = lib or load()
+    start = ctypes.addressof(ctypes.c_char.in_dll(lib, "p1hip_beloww_co"))
+    end = ctypes.addressof(ctypes.c_char.in_dll(lib, "p1hip_beloww_co_end"))
+    if end <= start:
+        raise P1HipError(-100, "embedded below wide code object is empty")
     return hashlib.sha256(ctypes.string_at(start, end - start)).hexdigest()
 
 

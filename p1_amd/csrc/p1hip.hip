@@ -51,9 +51,18 @@
 // layout, tables and decoder come from belowb_plan.hpp, which tools/batch_emu
 // shares.
 //
+// p1hip_scan_below_batch_wide: the same call with a third route.  The requests
+// whose first slice is sparse and of at most 2^24 nonces share k_scan launches
+// as the wide path's requests do; k_beloww_filter (a fifth code object,
+// p1hip_beloww_kernels.hip, p1hip_beloww_blob.S) turns each request's partials
+// into candidate tile indices on the device, and k_belowb_mark refines all
+// candidates of a device in one launch.  Routes, round items, groups, the slot
+// rule, tables and decoder come from beloww_plan.hpp, which tools/batch_emu
+// shares.
+//
 // Order of this file: runtime state, helpers, the scan path, the batch path,
 // the wide path, submit / wait, reduce_pairs, scan_tiles, scan_below,
-// scan_below_batch, then the C ABI in one extern "C" block.  Every HIP and RCCL
+// scan_below_batch, scan_below_batch_wide, then the C ABI in one extern "C" block.  Every HIP and RCCL
 // call of the library is in this file (tests/test_stream_discipline.py).
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -77,6 +86,7 @@
 #include "batch_plan.hpp"
 #include "below_plan.hpp"
 #include "belowb_plan.hpp"
+#include "beloww_plan.hpp"
 #include "planner.hpp"
 #include "scan_abi.hpp"
 #include "scan_pack.hpp"
@@ -84,11 +94,12 @@
 #include "wide_plan.hpp"
 
 // the embedded gfx950 code objects (p1hip_kernels_blob.S, p1hip_batch_blob.S,
-// p1hip_below_blob.S, p1hip_belowb_blob.S)
+// p1hip_below_blob.S, p1hip_belowb_blob.S, p1hip_beloww_blob.S)
 extern "C" const unsigned char p1hip_kernels_co[];
 extern "C" const unsigned char p1hip_batch_co[];
 extern "C" const unsigned char p1hip_below_co[];
 extern "C" const unsigned char p1hip_belowb_co[];
+extern "C" const unsigned char p1hip_beloww_co[];
 
 using namespace p1;
 
@@ -156,7 +167,7 @@ enum KnobId {
   kSmallMaxNoncesKnob, kMaxLaunchBlocksKnob, kMaxScanSpanKnob, kKwtabMaxBytesKnob, kNoRcclKnob, kForceRcclKnob,
   kMinFastThreadsKnob, kTestFailDeviceKnob, kNoTableKnob, kNoSplitKnob, kScanGridKnob, kBatchMaxNoncesKnob,
   kBatchMaxTilesKnob, kWideMaxNoncesKnob, kWideMaxSegsKnob, kWideMinFastThreadsKnob, kBelowPathKnob,
-  kBelowMaxSliceKnob, kKnobCount
+  kBelowMaxSliceKnob, kBelowWideMaxSlotsKnob, kKnobCount
 };
 struct Knob {
   const char* name;
@@ -212,6 +223,9 @@ const Knob kKnobs[] = {
     {"P1HIP_BELOW_MAX_SLICE", 0, ~0ull, kZeroDef, kPerScan,
      "nonces per slice of p1hip_scan_below at the most, below the route's own limit, so GPU tests run several "
      "slices, with hits next to their edges, on small ranges"},
+    {"P1HIP_BELOW_WIDE_MAX_SLOTS", 0, ~0ull, kZeroDef, kPerBatch,
+     "candidate slots per request and round of p1hip_scan_below_batch_wide at the most, below the slot rule's own "
+     "number (the default, 0), so GPU tests reach the host filter that answers a request with more candidates"},
 };
 static_assert(sizeof kKnobs / sizeof kKnobs[0] == kKnobCount, "one row per KnobId, in its order");
 
@@ -375,6 +389,27 @@ struct Dev {
   DevBuf<uint64_t> d_qmarks;    // kBelowWordsPerTile words per tile
   DevBuf<uint32_t> d_qout;
   PinnedBuf<uint32_t> h_qout;
+  // p1hip_scan_below_batch_wide: its own code object and buffers (phase A
+  // shares d_part, d_seg and the ticket with p1hip_scan, d_bseg with the batch
+  // and d_wrange with the wide call, as the wide call does).  d_ftab holds
+  // req_range0 (nreq + 1) and req_slot0 (nreq + 1); d_fcand the requests'
+  // counts and then their candidate slots; h_fpart the candidates' partials;
+  // the rest is phase B's mark launch.
+  hipModule_t fmod = nullptr;
+  hipFunction_t f_wfilter = nullptr;
+  DevBuf<uint32_t> d_ftab;
+  PinnedBuf<uint32_t> h_ftab;
+  DevBuf<uint64_t> d_ftarget;
+  PinnedBuf<uint64_t> h_ftarget;
+  DevBuf<uint32_t> d_fcand;
+  PinnedBuf<uint32_t> h_fcand;
+  PinnedBuf<Key> h_fpart;
+  DevBuf<BatchSeg> d_fseg;
+  PinnedBuf<BatchSeg> h_fseg;
+  DevBuf<uint64_t> d_fmtarget;
+  PinnedBuf<uint64_t> h_fmtarget;
+  DevBuf<uint64_t> d_fmarks;
+  PinnedBuf<uint64_t> h_fmarks;
   SlotDev slot[P1HIP_MAX_INFLIGHT];  // p1hip_batch_submit: one buffer set per ticket slot
   std::vector<hipEvent_t> evs;  // profiling event pool (pairs)
   // MODE 5 K+W tables on this device, least recently used first (built by
@@ -441,6 +476,7 @@ struct Runtime {
   p1hip_wide_stats_t wstats{};
   p1hip_below_stats_t lstats{};
   p1hip_below_batch_stats_t qstats{};
+  p1hip_below_wide_stats_t fstats{};
 };
 
 // Never destroyed: the runtime state outlives every static destructor, so a
@@ -538,6 +574,7 @@ int dev_release(Dev& d) {
   if (d.bmod) (void)hipModuleUnload(d.bmod);
   if (d.lmod) (void)hipModuleUnload(d.lmod);
   if (d.qmod) (void)hipModuleUnload(d.qmod);
+  if (d.fmod) (void)hipModuleUnload(d.fmod);
   d = Dev();  // every Buf frees itself here: this device is current, its work is done
   return 0;
 }
@@ -597,6 +634,8 @@ int init_devs(Runtime& R, const std::vector<int>& ords) {
     HIPCHK(hipModuleLoadData(&d.qmod, p1hip_belowb_co));
     HIPCHK(hipModuleGetFunction(&d.f_qmark, d.qmod, "k_belowb_mark"));
     HIPCHK(hipModuleGetFunction(&d.f_qcollect, d.qmod, "k_belowb_collect"));
+    HIPCHK(hipModuleLoadData(&d.fmod, p1hip_beloww_co));
+    HIPCHK(hipModuleGetFunction(&d.f_wfilter, d.fmod, "k_beloww_filter"));
     // fixed-size buffers: floor = need, so exactly that many elements
     HIPCHK(d.d_small_part.reserve(kSmallMaxBlocks, kSmallMaxBlocks));
     HIPCHK(d.d_ticket.reserve(1, 1));
@@ -1933,6 +1972,104 @@ int below_batch_enqueue(Dev& d, const BelowBLaunch& L, const BelowBTable& B, con
   return P1HIP_OK;
 }
 
+// The dense launch pairs of one round (p1hip_scan_below_batch;
+// p1hip_scan_below_batch_wide for its dense slices): the layout, every pair's
+// tables and where they lie in their device's buffers.
+struct BelowBRound {
+  std::vector<BelowBLaunch> launches;
+  std::vector<BelowBTable> tabs;
+  std::vector<BelowBPlace> place;
+  std::vector<BelowBPlace> need;  // per device: what the round takes of its buffers
+};
+
+// Lay the round's items out, build every table of the round, then each
+// device's buffers (its stream is idle: every round ends with a
+// synchronisation), then the enqueues and one copy back per device.  No
+// synchronisation.  `coalesced`: the call's requests BelowBItem::req indexes.
+int below_batch_round_enqueue(Runtime& R, const BelowBReq* q, const std::vector<size_t>& coalesced,
+                              const std::vector<BelowBItem>& items, BelowBRound& W, p1hip_below_batch_stats_t& add) {
+  const int ndev = (int)R.devs.size();
+  int rc;
+  W.launches = belowb_layout(items, ndev);
+  const std::vector<BelowBLaunch>& launches = W.launches;
+  W.tabs.resize(launches.size());
+  W.place.resize(launches.size());
+  W.need.assign((size_t)ndev, BelowBPlace{0, 0, 0, 0});
+  std::vector<size_t> max_tiles((size_t)ndev, 0);
+  for (size_t l = 0; l < launches.size(); ++l) {
+    const BelowBLaunch& L = launches[l];
+    const std::string err = belowb_build_table(q, coalesced, items, L, W.tabs[l]);
+    if (!err.empty()) return fail(P1HIP_ERR_ARGS, err);
+    if (L.tiles == 0 || L.tiles > kBatchMaxTiles || L.slots > kBelowBatchMaxSlots)
+      return fail(P1HIP_ERR_HIP, "internal: a below batch launch pair outside its limits");
+    BelowBPlace& N = W.need[(size_t)L.device];
+    W.place[l] = N;
+    N.seg0 += W.tabs[l].T.segs.size();
+    N.req0 += L.items.size();
+    N.tab0 += 2 * (L.items.size() + 1);
+    N.out0 += L.items.size() + (size_t)L.slots;
+    if (L.tiles > max_tiles[(size_t)L.device]) max_tiles[(size_t)L.device] = L.tiles;
+  }
+  for (int i = 0; i < ndev; ++i) {
+    const BelowBPlace& N = W.need[(size_t)i];
+    if (N.req0 == 0) continue;
+    Dev& d = R.devs[(size_t)i];
+    HIPCHK(hipSetDevice(d.ordinal));
+    HIPCHK(d.d_qseg.reserve(N.seg0, 64));
+    HIPCHK(d.h_qseg.reserve(N.seg0, 64));
+    HIPCHK(d.d_qtarget.reserve(N.req0, 64));
+    HIPCHK(d.h_qtarget.reserve(N.req0, 64));
+    HIPCHK(d.d_qtab.reserve(N.tab0, 128));
+    HIPCHK(d.h_qtab.reserve(N.tab0, 128));
+    HIPCHK(d.d_qmarks.reserve(max_tiles[(size_t)i] * kBelowWordsPerTile, 4096));
+    HIPCHK(d.d_qout.reserve(N.out0, 1024));
+    HIPCHK(d.h_qout.reserve(N.out0, 1024));
+  }
+  for (size_t l = 0; l < launches.size(); ++l) {
+    const BelowBLaunch& L = launches[l];
+    Dev& d = R.devs[(size_t)L.device];
+    HIPCHK(hipSetDevice(d.ordinal));
+    if ((rc = below_batch_enqueue(d, L, W.tabs[l], W.place[l])) != P1HIP_OK) return rc;
+    add.launches++;
+    add.tiles += L.tiles;
+    add.mark_nonces += W.tabs[l].T.nonces;
+    // the device's last pair of the round: the one copy back
+    if (l + 1 == launches.size() || launches[l + 1].device != L.device) {
+      const size_t words = W.need[(size_t)L.device].out0;
+      HIPCHK(hipMemcpyAsync(d.h_qout.p, d.d_qout.p, words * sizeof(uint32_t), hipMemcpyDeviceToHost, d.stream));
+      add.bytes_back += words * sizeof(uint32_t);
+    }
+  }
+  return P1HIP_OK;
+}
+
+// Wait for every device that took part in the round.
+int below_batch_round_sync(Runtime& R, const BelowBRound& W) {
+  for (size_t i = 0; i < W.need.size(); ++i)
+    if (W.need[i].req0) {
+      Dev& d = R.devs[i];
+      HIPCHK(hipSetDevice(d.ordinal));
+      HIPCHK(hipStreamSynchronize(d.stream));
+    }
+  return P1HIP_OK;
+}
+
+// Decode what the round's launch pairs returned (belowb_decode's checks):
+// each(item, its hits) for every item, in launch order.
+template <typename Fn>
+int below_batch_round_decode(Runtime& R, const BelowBRound& W, const std::vector<BelowBItem>& items, Fn&& each) {
+  std::vector<std::vector<Key>> got;
+  for (size_t l = 0; l < W.launches.size(); ++l) {
+    const BelowBLaunch& L = W.launches[l];
+    const uint32_t* out = R.devs[(size_t)L.device].h_qout.p + W.place[l].out0;
+    const std::string err = belowb_decode(W.tabs[l], out + L.items.size(), out, got);
+    if (!err.empty()) return fail(P1HIP_ERR_HIP, err);
+    for (size_t r = 0; r < L.items.size(); ++r)
+      if (int rc = each(items[L.items[r]], got[r])) return rc;
+  }
+  return P1HIP_OK;
+}
+
 int scan_below_batch_locked(const p1hip_below_request_t* reqs, size_t n, const std::vector<size_t>& off,
                             p1hip_result_t* hits, size_t* found) {
   Runtime& R = rt();
@@ -1955,96 +2092,33 @@ int scan_below_batch_locked(const p1hip_below_request_t* reqs, size_t n, const s
   auto run = [&]() -> int {
     if (coalesced.empty() && individual.empty()) return P1HIP_OK;  // all empty: no device
     if ((rc = ensure_init(R))) return rc;
-    const int ndev = (int)R.devs.size();
     std::vector<BelowBState> st(coalesced.size());
     for (size_t j = 0; j < coalesced.size(); ++j) st[j] = {q[coalesced[j]].lower, 0, false};
     std::vector<BelowBItem> items;
-    std::vector<BelowBTable> tabs;
-    std::vector<BelowBPlace> place;
-    std::vector<std::vector<Key>> got;
+    BelowBRound W;
     for (size_t left = coalesced.size(); left > 0;) {
-      std::string err = belowb_round_items(q.data(), coalesced, st, path, max_slice, items);
+      const std::string err = belowb_round_items(q.data(), coalesced, st, path, max_slice, items);
       if (!err.empty()) return fail(P1HIP_ERR_HIP, err);
-      const std::vector<BelowBLaunch> launches = belowb_layout(items, ndev);
-      // every table of the round, then each device's buffers (its stream is
-      // idle: every round ends with a synchronisation), then the enqueues
-      tabs.resize(launches.size());
-      place.resize(launches.size());
-      std::vector<BelowBPlace> need((size_t)ndev, BelowBPlace{0, 0, 0, 0});
-      std::vector<size_t> max_tiles((size_t)ndev, 0);
-      for (size_t l = 0; l < launches.size(); ++l) {
-        const BelowBLaunch& L = launches[l];
-        err = belowb_build_table(q.data(), coalesced, items, L, tabs[l]);
-        if (!err.empty()) return fail(P1HIP_ERR_ARGS, err);
-        if (L.tiles == 0 || L.tiles > kBatchMaxTiles || L.slots > kBelowBatchMaxSlots)
-          return fail(P1HIP_ERR_HIP, "internal: a below batch launch pair outside its limits");
-        BelowBPlace& N = need[(size_t)L.device];
-        place[l] = N;
-        N.seg0 += tabs[l].T.segs.size();
-        N.req0 += L.items.size();
-        N.tab0 += 2 * (L.items.size() + 1);
-        N.out0 += L.items.size() + (size_t)L.slots;
-        if (L.tiles > max_tiles[(size_t)L.device]) max_tiles[(size_t)L.device] = L.tiles;
-      }
-      for (int i = 0; i < ndev; ++i) {
-        const BelowBPlace& N = need[(size_t)i];
-        if (N.req0 == 0) continue;
-        Dev& d = R.devs[(size_t)i];
-        HIPCHK(hipSetDevice(d.ordinal));
-        HIPCHK(d.d_qseg.reserve(N.seg0, 64));
-        HIPCHK(d.h_qseg.reserve(N.seg0, 64));
-        HIPCHK(d.d_qtarget.reserve(N.req0, 64));
-        HIPCHK(d.h_qtarget.reserve(N.req0, 64));
-        HIPCHK(d.d_qtab.reserve(N.tab0, 128));
-        HIPCHK(d.h_qtab.reserve(N.tab0, 128));
-        HIPCHK(d.d_qmarks.reserve(max_tiles[(size_t)i] * kBelowWordsPerTile, 4096));
-        HIPCHK(d.d_qout.reserve(N.out0, 1024));
-        HIPCHK(d.h_qout.reserve(N.out0, 1024));
-      }
-      for (size_t l = 0; l < launches.size(); ++l) {
-        const BelowBLaunch& L = launches[l];
-        Dev& d = R.devs[(size_t)L.device];
-        HIPCHK(hipSetDevice(d.ordinal));
-        if ((rc = below_batch_enqueue(d, L, tabs[l], place[l])) != P1HIP_OK) return rc;
-        add.launches++;
-        add.tiles += L.tiles;
-        add.mark_nonces += tabs[l].T.nonces;
-        // the device's last pair of the round: the one copy back
-        if (l + 1 == launches.size() || launches[l + 1].device != L.device) {
-          const size_t words = need[(size_t)L.device].out0;
-          HIPCHK(hipMemcpyAsync(d.h_qout.p, d.d_qout.p, words * sizeof(uint32_t), hipMemcpyDeviceToHost, d.stream));
-          add.bytes_back += words * sizeof(uint32_t);
+      if ((rc = below_batch_round_enqueue(R, q.data(), coalesced, items, W, add)) != P1HIP_OK) return rc;
+      if ((rc = below_batch_round_sync(R, W)) != P1HIP_OK) return rc;
+      rc = below_batch_round_decode(R, W, items, [&](const BelowBItem& it, const std::vector<Key>& got) -> int {
+        BelowBState& S = st[it.req];
+        const size_t i = coalesced[it.req];
+        for (const Key& k : got) {
+          if (!res[i].empty() && k.n <= res[i].back().nonce)
+            return fail(P1HIP_ERR_HIP, "collect check: request " + std::to_string(i) + " has nonces out of order");
+          res[i].push_back({k.h, k.n});
         }
-      }
-      for (int i = 0; i < ndev; ++i)
-        if (need[(size_t)i].req0) {
-          Dev& d = R.devs[(size_t)i];
-          HIPCHK(hipSetDevice(d.ordinal));
-          HIPCHK(hipStreamSynchronize(d.stream));
+        S.found += got.size();
+        if (S.found == q[i].cap || it.hi == q[i].upper) {
+          S.done = true;
+          --left;
+        } else {
+          S.lo = it.hi + 1;
         }
-      for (size_t l = 0; l < launches.size(); ++l) {
-        const BelowBLaunch& L = launches[l];
-        const uint32_t* out = R.devs[(size_t)L.device].h_qout.p + place[l].out0;
-        err = belowb_decode(tabs[l], out + L.items.size(), out, got);
-        if (!err.empty()) return fail(P1HIP_ERR_HIP, err);
-        for (size_t r = 0; r < L.items.size(); ++r) {
-          const BelowBItem& it = items[L.items[r]];
-          BelowBState& S = st[it.req];
-          const size_t i = coalesced[it.req];
-          for (const Key& k : got[r]) {
-            if (!res[i].empty() && k.n <= res[i].back().nonce)
-              return fail(P1HIP_ERR_HIP, "collect check: request " + std::to_string(i) + " has nonces out of order");
-            res[i].push_back({k.h, k.n});
-          }
-          S.found += got[r].size();
-          if (S.found == q[i].cap || it.hi == q[i].upper) {
-            S.done = true;
-            --left;
-          } else {
-            S.lo = it.hi + 1;
-          }
-        }
-      }
+        return P1HIP_OK;
+      });
+      if (rc != P1HIP_OK) return rc;
       add.rounds++;
     }
     // The other requests: one by one through p1hip_scan_below's own path.
@@ -2111,6 +2185,424 @@ int below_collect_locked(const uint64_t* words, const uint32_t* req_tile0, const
   HIPCHK(hipMemcpyAsync(hc.data(), dc.p, nreq * sizeof(uint32_t), hipMemcpyDeviceToHost, d.stream));
   HIPCHK(hipStreamSynchronize(d.stream));
   for (size_t i = 0; i < nslots; ++i) idx[i] = hx[i];
+  for (size_t i = 0; i < nreq; ++i) count[i] = hc[i];
+  return P1HIP_OK;
+}
+
+// ----------------------------------------------------------------------------
+// p1hip_scan_below_batch_wide
+// ----------------------------------------------------------------------------
+static_assert(P1HIP_BELOW_WIDE_MAX_NONCES == kWideMaxNonces, "p1hip.h and wide_plan.hpp disagree");
+
+// One device's part of one group of sparse slices: the filter's tables, what
+// phase B refines and the mark launch in flight.
+struct BelowWWork {
+  BelowWFilter F;
+  BelowWRefine X;
+  std::vector<char> known;  // per candidate: its partial is already in X (the host filter's)
+  std::vector<BelowHit> hits;
+  size_t next = 0;  // first piece of X not yet marked
+  BelowTable B;     // the table in flight
+  std::vector<uint64_t> targets;
+  bool busy = false;
+};
+
+// Phase A of device d: the tables, one k_batch_scan for the generic pieces, the
+// shared k_scan launches (wide_enqueue's, in the same buffers: d_part, d_seg and
+// the ticket are p1hip_scan's, d_bseg the batch's, d_wrange the wide call's),
+// then k_beloww_filter and the copy back of one count per request and its
+// candidate slots.  No synchronisation.  The stream may still run the round's
+// dense launch pairs, which use none of the buffers grown here.
+int beloww_enqueue(Dev& d, const WideDevice& D, const BelowWFilter& F, p1hip_below_wide_stats_t& add) {
+  const size_t nreq = D.reqs.size(), nslot = F.req_slot0[nreq];
+  HIPCHK(hipSetDevice(d.ordinal));
+  HIPCHK(d.d_part.reserve(D.total_tiles, 1));
+  HIPCHK(d.d_seg.reserve(D.fast.size(), 4 * kMaxSegs));
+  HIPCHK(d.h_seg.reserve(D.fast.size(), 4 * kMaxSegs));
+  HIPCHK(d.d_bseg.reserve(D.gsegs.size(), 64));
+  HIPCHK(d.h_bseg.reserve(D.gsegs.size(), 64));
+  HIPCHK(d.d_wrange.reserve(D.ranges.size(), 64));
+  HIPCHK(d.h_wrange.reserve(D.ranges.size(), 64));
+  HIPCHK(d.d_ftab.reserve(2 * (nreq + 1), 128));
+  HIPCHK(d.h_ftab.reserve(2 * (nreq + 1), 128));
+  HIPCHK(d.d_ftarget.reserve(nreq, 64));
+  HIPCHK(d.h_ftarget.reserve(nreq, 64));
+  HIPCHK(d.d_fcand.reserve(nreq + nslot, 1024));
+  HIPCHK(d.h_fcand.reserve(nreq + nslot, 1024));
+  for (const WideLaunch& W : D.launches) {
+    const std::string err = wide_fill_launch(D, W, d.h_seg.p + W.first);
+    if (!err.empty()) return fail(P1HIP_ERR_ARGS, err);
+  }
+  if (!D.fast.empty())
+    HIPCHK(hipMemcpyAsync(d.d_seg.p, d.h_seg.p, D.fast.size() * sizeof(Segment), hipMemcpyHostToDevice, d.stream));
+  memcpy(d.h_wrange.p, D.ranges.data(), D.ranges.size() * sizeof(WideRange));
+  memcpy(d.h_ftab.p, D.req_range0.data(), (nreq + 1) * sizeof(uint32_t));
+  memcpy(d.h_ftab.p + nreq + 1, F.req_slot0.data(), (nreq + 1) * sizeof(uint32_t));
+  memcpy(d.h_ftarget.p, F.targets.data(), nreq * sizeof(uint64_t));
+  HIPCHK(hipMemcpyAsync(d.d_wrange.p, d.h_wrange.p, D.ranges.size() * sizeof(WideRange), hipMemcpyHostToDevice, d.stream));
+  HIPCHK(hipMemcpyAsync(d.d_ftab.p, d.h_ftab.p, 2 * (nreq + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, d.stream));
+  HIPCHK(hipMemcpyAsync(d.d_ftarget.p, d.h_ftarget.p, nreq * sizeof(uint64_t), hipMemcpyHostToDevice, d.stream));
+  if (D.gen_tiles) {
+    memcpy(d.h_bseg.p, D.gsegs.data(), D.gsegs.size() * sizeof(BatchSeg));
+    HIPCHK(hipMemcpyAsync(d.d_bseg.p, d.h_bseg.p, D.gsegs.size() * sizeof(BatchSeg), hipMemcpyHostToDevice, d.stream));
+    HIPCHK(launch(d.f_bscan, D.gen_tiles, kBlock, d.stream, (const BatchSeg*)d.d_bseg.p, (uint32_t)D.gsegs.size(),
+                  (Key*)(d.d_part.p + D.gen_tile0)));
+  }
+  for (const WideLaunch& W : D.launches) {
+#ifdef P1_STATIC_GRID
+    HIPCHK(launch(d.f_scan, W.tiles, kBlock, d.stream, (const Segment*)(d.d_seg.p + W.first), (uint32_t)W.count,
+                  (Key*)(d.d_part.p + W.tile0)));
+#else
+    HIPCHK(launch(d.f_scan, scan_grid_for(d, W.tiles), kBlock, d.stream, (const Segment*)(d.d_seg.p + W.first),
+                  (uint32_t)W.count, (Key*)(d.d_part.p + W.tile0), (uint32_t)W.tiles, d.d_scan_ticket.p));
+#endif
+  }
+  HIPCHK(launch(d.f_wfilter, (uint32_t)nreq, kBlock, d.stream, (const Key*)d.d_part.p, (const WideRange*)d.d_wrange.p,
+                (const uint32_t*)d.d_ftab.p, (const uint64_t*)d.d_ftarget.p, (const uint32_t*)(d.d_ftab.p + nreq + 1),
+                d.d_fcand.p + nreq, d.d_fcand.p));
+  HIPCHK(hipMemcpyAsync(d.h_fcand.p, d.d_fcand.p, (nreq + nslot) * sizeof(uint32_t), hipMemcpyDeviceToHost, d.stream));
+  uint64_t fast_nonces = 0;
+  for (const WideFast& f : D.fast) fast_nonces += D.plans[f.req].launches[f.piece].nonces;
+  d.acc.scan_launches += D.launches.size();
+  d.acc.scan_nonces += fast_nonces;
+  add.scan_launches += D.launches.size();
+  add.scan_segments += D.fast.size();
+  add.generic_launches += D.gen_tiles ? 1 : 0;
+  add.scan_nonces += D.nonces;
+  add.filter_launches++;
+  add.bytes_back += (nreq + nslot) * sizeof(uint32_t);
+  return P1HIP_OK;
+}
+
+// After phase A of device d is synchronised: every request's candidates into
+// W.X.  A request that reports more candidates than it has slots is filtered
+// here instead: its ranges of the partial array, which are still on the device,
+// are copied back and walked with the kernel's own per-thread function.  The
+// partials of the other candidates are fetched (16 bytes each, neighbours in
+// one copy) into d.h_fpart; that copy is enqueued, not waited for.
+int beloww_candidates(Dev& d, const std::vector<size_t>& live, const std::vector<BelowWItem>& sparse,
+                      const BelowWGroup& G, size_t dv, BelowWWork& W, p1hip_below_wide_stats_t& add) {
+  const WideDevice& D = G.Y.devs[dv];
+  const size_t nreq = D.reqs.size();
+  HIPCHK(hipSetDevice(d.ordinal));
+  const uint32_t* count = d.h_fcand.p;
+  const uint32_t* cand = d.h_fcand.p + nreq;
+  std::vector<Key> hpart;
+  std::vector<uint32_t> idx;
+  for (uint32_t r = 0; r < (uint32_t)nreq; ++r) {
+    const size_t i = live[sparse[G.members[D.reqs[r]]].req];
+    const uint32_t s0 = W.F.req_slot0[r], slots = W.F.req_slot0[r + 1] - s0;
+    const size_t before = W.X.cand_req.size();
+    const bool overflow = count[r] > slots;
+    std::string err;
+    if (!overflow) {
+      err = beloww_add_candidates(D, W.F, r, i, cand + s0, count[r], W.X);
+    } else {
+      add.slot_overflows++;
+      hpart.resize(D.total_tiles);
+      for (uint32_t j = D.req_range0[r]; j < D.req_range0[r + 1]; ++j) {
+        const WideRange Rg = D.ranges[j];
+        HIPCHK(hipMemcpyAsync(hpart.data() + Rg.tile0, d.d_part.p + Rg.tile0, (size_t)Rg.ntiles * sizeof(Key),
+                              hipMemcpyDeviceToHost, d.stream));
+        add.bytes_back += (uint64_t)Rg.ntiles * sizeof(Key);
+      }
+      HIPCHK(hipStreamSynchronize(d.stream));
+      idx.clear();
+      for (uint32_t j = D.req_range0[r]; j < D.req_range0[r + 1]; ++j) {
+        const WideRange Rg = D.ranges[j];
+        for (uint32_t t = 0; t < Rg.ntiles; ++t) {
+          uint32_t tile;
+          if (beloww_thread(hpart.data(), Rg, 0, t, W.F.targets[r], &tile)) idx.push_back(tile);
+        }
+      }
+      if (idx.size() != count[r])
+        return fail(P1HIP_ERR_HIP, "filter check: request " + std::to_string(i) + " reports " + std::to_string(count[r]) +
+                                       " candidates, its partials hold " + std::to_string(idx.size()));
+      err = beloww_add_candidates(D, W.F, r, i, idx.data(), (uint32_t)idx.size(), W.X);
+    }
+    if (!err.empty()) return fail(P1HIP_ERR_HIP, err);
+    W.known.resize(W.X.cand_req.size(), overflow);
+    if (overflow)
+      for (size_t c = before; c < W.X.cand_req.size(); ++c) W.X.cand_part[c] = hpart[W.X.cand_tile[c]];
+  }
+  const size_t ncand = W.X.cand_req.size();
+  add.candidate_tiles += ncand;
+  HIPCHK(d.h_fpart.reserve(ncand, 64));
+  for (size_t c = 0; c < ncand;) {
+    size_t e = c + 1;
+    if (!W.known[c]) {
+      while (e < ncand && !W.known[e] && W.X.cand_tile[e] == W.X.cand_tile[e - 1] + 1) ++e;
+      HIPCHK(hipMemcpyAsync(d.h_fpart.p + c, d.d_part.p + W.X.cand_tile[c], (e - c) * sizeof(Key), hipMemcpyDeviceToHost,
+                            d.stream));
+      add.bytes_back += (e - c) * sizeof(Key);
+    }
+    c = e;
+  }
+  return P1HIP_OK;
+}
+
+// Phase B of device d, one step: the k_belowb_mark table that starts at piece
+// W.next, the kernel, the marks back whole.  No synchronisation.  The buffers
+// are this path's own; the stream runs nothing that uses them.
+int beloww_mark_enqueue(Dev& d, const BelowBReq* q, BelowWWork& W, p1hip_below_wide_stats_t& add) {
+  const std::string err = beloww_build_table(q, W.X, W.next, W.B, W.targets);
+  if (!err.empty()) return fail(P1HIP_ERR_ARGS, err);
+  if (W.B.count == 0 || W.B.tiles == 0) return fail(P1HIP_ERR_HIP, "internal: empty refine table");
+  const size_t nseg = W.B.T.segs.size(), words = (size_t)W.B.tiles * kBelowWordsPerTile;
+  HIPCHK(hipSetDevice(d.ordinal));
+  HIPCHK(d.d_fseg.reserve(nseg, 64));
+  HIPCHK(d.h_fseg.reserve(nseg, 64));
+  HIPCHK(d.d_fmtarget.reserve(W.B.count, 64));
+  HIPCHK(d.h_fmtarget.reserve(W.B.count, 64));
+  HIPCHK(d.d_fmarks.reserve(words, 4096));
+  HIPCHK(d.h_fmarks.reserve(words, 4096));
+  memcpy(d.h_fseg.p, W.B.T.segs.data(), nseg * sizeof(BatchSeg));
+  memcpy(d.h_fmtarget.p, W.targets.data(), W.B.count * sizeof(uint64_t));
+  HIPCHK(hipMemcpyAsync(d.d_fseg.p, d.h_fseg.p, nseg * sizeof(BatchSeg), hipMemcpyHostToDevice, d.stream));
+  HIPCHK(hipMemcpyAsync(d.d_fmtarget.p, d.h_fmtarget.p, W.B.count * sizeof(uint64_t), hipMemcpyHostToDevice, d.stream));
+  HIPCHK(launch(d.f_qmark, W.B.tiles, kBlock, d.stream, (const BatchSeg*)d.d_fseg.p, (uint32_t)nseg,
+                (const uint64_t*)d.d_fmtarget.p, d.d_fmarks.p));
+  HIPCHK(hipMemcpyAsync(d.h_fmarks.p, d.d_fmarks.p, words * sizeof(uint64_t), hipMemcpyDeviceToHost, d.stream));
+  W.busy = true;
+  add.mark_launches++;
+  add.mark_tiles += W.B.tiles;
+  add.mark_nonces += W.B.T.nonces;
+  add.bytes_back += words * sizeof(uint64_t);
+  return P1HIP_OK;
+}
+
+// The routes of a call and the states of its live (coalesced and filtered) requests.
+void beloww_routes(const std::vector<BelowBReq>& q, int path, uint64_t max_slice, std::vector<int>& route,
+                   std::vector<size_t>& live, std::vector<BelowWState>& st) {
+  route.resize(q.size());
+  for (size_t i = 0; i < q.size(); ++i) {
+    route[i] = beloww_route(q[i], path, max_slice);
+    if (route[i] == kBelowWCoalesced || route[i] == kBelowWFiltered) {
+      live.push_back(i);
+      st.push_back(beloww_state(q[i], route[i], path, max_slice));
+    }
+  }
+}
+
+int scan_below_batch_wide_locked(const p1hip_below_request_t* reqs, size_t n, const std::vector<size_t>& off,
+                                 p1hip_result_t* hits, size_t* found) {
+  Runtime& R = rt();
+  std::lock_guard<std::mutex> g(R.mu);
+  const auto t0 = std::chrono::steady_clock::now();
+  const int path = (int)knob(kBelowPathKnob);
+  const uint64_t max_slice = knob(kBelowMaxSliceKnob);
+  const uint32_t max_segs = (uint32_t)knob(kWideMaxSegsKnob);
+  const uint64_t floor = knob(kWideMinFastThreadsKnob), max_slots = knob(kBelowWideMaxSlotsKnob);
+  const std::vector<BelowBReq> q = below_batch_reqs(reqs, n);
+  p1hip_below_wide_stats_t add{};
+  std::vector<int> route;
+  std::vector<size_t> live, individual;
+  std::vector<BelowWState> st;
+  beloww_routes(q, path, max_slice, route, live, st);
+  for (size_t i = 0; i < n; ++i) {
+    add.empty += route[i] == kBelowWEmpty;
+    add.coalesced += route[i] == kBelowWCoalesced;
+    add.filtered += route[i] == kBelowWFiltered;
+    if (route[i] == kBelowWIndividual) individual.push_back(i);
+  }
+  // results are gathered here and copied to `hits` only when the whole call has succeeded
+  std::vector<std::vector<p1hip_result_t>> res(n);
+  int rc;
+  // the hits got[0 .. ngot) (in increasing nonce) of live request j, whose slice ended at `hi`
+  size_t left = live.size();
+  auto take = [&](size_t j, uint64_t hi, const Key* got, size_t ngot) -> int {
+    const size_t i = live[j];
+    for (size_t k = 0; k < ngot; ++k) {
+      if (!res[i].empty() && got[k].n <= res[i].back().nonce)
+        return fail(P1HIP_ERR_HIP, "collect check: request " + std::to_string(i) + " has nonces out of order");
+      res[i].push_back({got[k].h, got[k].n});
+    }
+    st[j].found += ngot;
+    if (st[j].found == q[i].cap || hi == q[i].upper) {
+      st[j].done = true;
+      --left;
+    } else {
+      st[j].lo = hi + 1;
+    }
+    return P1HIP_OK;
+  };
+  auto run = [&]() -> int {
+    if (live.empty() && individual.empty()) return P1HIP_OK;  // all empty: no device
+    if ((rc = ensure_init(R))) return rc;
+    const int ndev = (int)R.devs.size();
+    std::vector<BelowBItem> dense;
+    std::vector<BelowWItem> sparse;
+    BelowBRound DR;
+    BelowWGroup G;
+    std::vector<BelowWWork> work;
+    std::vector<std::vector<Key>> got(n);
+    while (left > 0) {
+      std::string err = beloww_round_items(q.data(), live, st, path, max_slice, dense, sparse);
+      if (!err.empty()) return fail(P1HIP_ERR_HIP, err);
+      // the dense slices: p1hip_scan_below_batch's launch pairs, decoded at the end of the round
+      if (!dense.empty()) {
+        p1hip_below_batch_stats_t dadd{};
+        if ((rc = below_batch_round_enqueue(R, q.data(), live, dense, DR, dadd)) != P1HIP_OK) return rc;
+        add.mark_launches += dadd.launches;
+        add.mark_tiles += dadd.tiles;
+        add.mark_nonces += dadd.mark_nonces;
+        add.bytes_back += dadd.bytes_back;
+      }
+      // the sparse slices, group after group
+      std::vector<size_t> pending(sparse.size());
+      for (size_t s = 0; s < sparse.size(); ++s) pending[s] = s;
+      while (!pending.empty()) {
+        err = beloww_next_group(q.data(), live, sparse, pending, ndev, max_segs, floor, R.split, kWideMaxTiles, G);
+        if (!err.empty()) return fail(P1HIP_ERR_ARGS, err);
+        add.groups++;
+        work.clear();
+        work.resize((size_t)ndev);
+        // phase A: every device enqueued before any is synchronised
+        for (int dv = 0; dv < ndev; ++dv) {
+          if (G.Y.devs[(size_t)dv].reqs.empty()) continue;
+          err = beloww_filter_tables(q.data(), live, sparse, G, (size_t)dv, max_slots, work[(size_t)dv].F);
+          if (!err.empty()) return fail(P1HIP_ERR_HIP, err);
+          if ((rc = beloww_enqueue(R.devs[(size_t)dv], G.Y.devs[(size_t)dv], work[(size_t)dv].F, add)) != P1HIP_OK) return rc;
+        }
+        for (int dv = 0; dv < ndev; ++dv) {
+          if (G.Y.devs[(size_t)dv].reqs.empty()) continue;
+          Dev& d = R.devs[(size_t)dv];
+          HIPCHK(hipSetDevice(d.ordinal));
+          HIPCHK(hipStreamSynchronize(d.stream));
+          if ((rc = beloww_candidates(d, live, sparse, G, (size_t)dv, work[(size_t)dv], add)) != P1HIP_OK) return rc;
+        }
+        // phase B: one mark launch per device at a time, on the requests' own device
+        for (bool any = true; any;) {
+          any = false;
+          for (int dv = 0; dv < ndev; ++dv) {
+            BelowWWork& W = work[(size_t)dv];
+            if (W.next >= W.X.pieces.size()) continue;
+            if ((rc = beloww_mark_enqueue(R.devs[(size_t)dv], q.data(), W, add)) != P1HIP_OK) return rc;
+            any = true;
+          }
+          for (int dv = 0; dv < ndev; ++dv) {
+            BelowWWork& W = work[(size_t)dv];
+            if (!W.busy) continue;
+            Dev& d = R.devs[(size_t)dv];
+            HIPCHK(hipSetDevice(d.ordinal));
+            HIPCHK(hipStreamSynchronize(d.stream));
+            W.busy = false;
+            err = beloww_decode(W.B, W.X, d.h_fmarks.p, W.targets, W.hits);
+            if (!err.empty()) return fail(P1HIP_ERR_HIP, err);
+            W.next += W.B.count;
+          }
+        }
+        for (int dv = 0; dv < ndev; ++dv) {
+          const WideDevice& D = G.Y.devs[(size_t)dv];
+          if (D.reqs.empty()) continue;
+          BelowWWork& W = work[(size_t)dv];
+          for (size_t c = 0; c < W.X.cand_req.size(); ++c)
+            if (!W.known[c]) W.X.cand_part[c] = R.devs[(size_t)dv].h_fpart.p[c];
+          err = beloww_check_parts(q.data(), W.X);
+          if (err.empty()) err = beloww_finish(W.X, W.hits);
+          if (!err.empty()) return fail(P1HIP_ERR_HIP, err);
+          for (const BelowHit& h : W.hits) got[W.X.cand_req[h.cand]].push_back(h.key);
+          for (size_t r = 0; r < D.reqs.size(); ++r) {
+            const BelowWItem& it = sparse[G.members[D.reqs[r]]];
+            std::vector<Key>& mine = got[live[it.req]];
+            if ((rc = take(it.req, it.hi, mine.data(), (size_t)std::min<uint64_t>(it.want, mine.size()))) != P1HIP_OK)
+              return rc;
+            mine.clear();
+          }
+        }
+      }
+      if (!dense.empty()) {
+        if ((rc = below_batch_round_sync(R, DR)) != P1HIP_OK) return rc;
+        rc = below_batch_round_decode(R, DR, dense, [&](const BelowBItem& it, const std::vector<Key>& hs) -> int {
+          return take(it.req, it.hi, hs.data(), hs.size());
+        });
+        if (rc != P1HIP_OK) return rc;
+      }
+      add.rounds++;
+    }
+    // The other requests: one by one through p1hip_scan_below's own path.
+    for (size_t i : individual)
+      if ((rc = scan_below_held(R, q[i].msg, q[i].len, q[i].lower, q[i].upper, q[i].target, (size_t)q[i].cap, res[i])))
+        return fail(rc, "request " + std::to_string(i) + ": " + g_err);
+    return P1HIP_OK;
+  };
+  if ((rc = run()) != P1HIP_OK) {
+    // leave nothing in flight behind a failed call: the next call rewrites the pinned staging tables
+    const std::string keep = g_err;
+    for (Dev& d : R.devs) (void)hipStreamSynchronize(d.stream);
+    g_err = keep;
+    return rc;
+  }
+  for (size_t i = 0; i < n; ++i) {
+    for (size_t k = 0; k < res[i].size(); ++k) hits[off[i] + k] = res[i][k];
+    found[i] = res[i].size();
+    add.hits += res[i].size();
+  }
+  p1hip_below_wide_stats_t& T = R.fstats;
+  T.calls++;
+  T.requests += n;
+  T.empty += add.empty;
+  T.coalesced += add.coalesced;
+  T.filtered += add.filtered;
+  T.individual += individual.size();
+  T.rounds += add.rounds;
+  T.groups += add.groups;
+  T.scan_launches += add.scan_launches;
+  T.scan_segments += add.scan_segments;
+  T.generic_launches += add.generic_launches;
+  T.scan_nonces += add.scan_nonces;
+  T.filter_launches += add.filter_launches;
+  T.candidate_tiles += add.candidate_tiles;
+  T.slot_overflows += add.slot_overflows;
+  T.mark_launches += add.mark_launches;
+  T.mark_tiles += add.mark_tiles;
+  T.mark_nonces += add.mark_nonces;
+  T.hits += add.hits;
+  T.bytes_back += add.bytes_back;
+  T.wall_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return P1HIP_OK;
+}
+
+// p1hip_below_filter (test hook): k_beloww_filter alone on the first device, in
+// scratch of exactly this call's size, as below_collect_locked's.
+int below_filter_locked(const uint64_t* part_hash, const uint64_t* part_nonce, size_t ntiles, const uint32_t* range_tile0,
+                        const uint32_t* range_ntiles, const uint32_t* req_range0, const uint64_t* targets,
+                        const uint32_t* req_slot0, size_t nreq, uint32_t* cand, uint32_t* count) {
+  Runtime& R = rt();
+  std::lock_guard<std::mutex> g(R.mu);
+  int rc = ensure_init(R);
+  if (rc) return rc;
+  Dev& d = R.devs[0];
+  HIPCHK(hipSetDevice(d.ordinal));
+  const size_t nrange = req_range0[nreq], nslot = req_slot0[nreq];
+  std::vector<Key> hp(ntiles);
+  for (size_t t = 0; t < ntiles; ++t) hp[t] = Key{part_hash[t], part_nonce[t]};
+  std::vector<WideRange> hr(nrange);
+  for (size_t j = 0; j < nrange; ++j) hr[j] = WideRange{range_tile0[j], range_ntiles[j]};
+  DevBuf<Key> dp;
+  DevBuf<WideRange> dr;
+  DevBuf<uint64_t> dt;
+  DevBuf<uint32_t> dtab, dx, dc;
+  HIPCHK(dp.reserve(ntiles + 1, ntiles + 1));
+  HIPCHK(dr.reserve(nrange + 1, nrange + 1));
+  HIPCHK(dt.reserve(nreq, nreq));
+  HIPCHK(dtab.reserve(2 * (nreq + 1), 2 * (nreq + 1)));
+  HIPCHK(dx.reserve(nslot + 1, nslot + 1));
+  HIPCHK(dc.reserve(nreq, nreq));
+  if (ntiles) HIPCHK(hipMemcpyAsync(dp.p, hp.data(), ntiles * sizeof(Key), hipMemcpyHostToDevice, d.stream));
+  if (nrange) HIPCHK(hipMemcpyAsync(dr.p, hr.data(), nrange * sizeof(WideRange), hipMemcpyHostToDevice, d.stream));
+  HIPCHK(hipMemcpyAsync(dt.p, targets, nreq * sizeof(uint64_t), hipMemcpyHostToDevice, d.stream));
+  HIPCHK(hipMemcpyAsync(dtab.p, req_range0, (nreq + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, d.stream));
+  HIPCHK(hipMemcpyAsync(dtab.p + nreq + 1, req_slot0, (nreq + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, d.stream));
+  // only for the hook: a slot the kernel leaves alone reads UINT32_MAX
+  HIPCHK(hipMemsetAsync(dx.p, 0xff, (nslot + 1) * sizeof(uint32_t), d.stream));
+  HIPCHK(launch(d.f_wfilter, (uint32_t)nreq, kBlock, d.stream, (const Key*)dp.p, (const WideRange*)dr.p,
+                (const uint32_t*)dtab.p, (const uint64_t*)dt.p, (const uint32_t*)(dtab.p + nreq + 1), dx.p, dc.p));
+  std::vector<uint32_t> hx(nslot), hc(nreq);
+  if (nslot) HIPCHK(hipMemcpyAsync(hx.data(), dx.p, nslot * sizeof(uint32_t), hipMemcpyDeviceToHost, d.stream));
+  HIPCHK(hipMemcpyAsync(hc.data(), dc.p, nreq * sizeof(uint32_t), hipMemcpyDeviceToHost, d.stream));
+  HIPCHK(hipStreamSynchronize(d.stream));
+  for (size_t i = 0; i < nslot; ++i) cand[i] = hx[i];
   for (size_t i = 0; i < nreq; ++i) count[i] = hc[i];
   return P1HIP_OK;
 }
@@ -2267,6 +2759,111 @@ int p1hip_below_collect(const uint64_t* words, const uint32_t* req_tile0, const 
     return fail(P1HIP_ERR_ARGS, "more than 2^20 tiles or 2^22 slots");
   if ((!words && req_tile0[nreq] > 0) || (!idx && req_hit0[nreq] > 0)) return fail(P1HIP_ERR_ARGS, "null words or idx array");
   return guarded([&]() { return below_collect_locked(words, req_tile0, req_hit0, nreq, idx, count); });
+}
+
+int p1hip_scan_below_batch_wide(const p1hip_below_request_t* reqs, size_t n, p1hip_result_t* hits, size_t hits_len,
+                                size_t* found) {
+  if (n == 0) return P1HIP_OK;
+  if (!reqs || !found) return fail(P1HIP_ERR_ARGS, "null request or found array");
+  return guarded([&]() {
+    if (int rc = below_batch_check(reqs, n)) return rc;
+    std::vector<size_t> off(n);
+    size_t total = 0;
+    for (size_t i = 0; i < n; ++i) {
+      off[i] = total;
+      if (__builtin_add_overflow(total, reqs[i].cap, &total))
+        return fail(P1HIP_ERR_ARGS, "request " + std::to_string(i) + ": the sum of the caps overflows");
+    }
+    if (total > hits_len)
+      return fail(P1HIP_ERR_ARGS, "the caps add up to " + std::to_string(total) + ", hits_len is " + std::to_string(hits_len));
+    if (!hits && total > 0) return fail(P1HIP_ERR_ARGS, "null hits array");
+    return scan_below_batch_wide_locked(reqs, n, off, hits, found);
+  });
+}
+
+int p1hip_below_wide_layout(const p1hip_below_request_t* reqs, size_t n, int ndev, int32_t* route, int32_t* device,
+                            uint32_t* tiles, uint32_t* slots) {
+  if (ndev <= 0) return fail(P1HIP_ERR_ARGS, "ndev <= 0");
+  if (n == 0) return P1HIP_OK;
+  if (!reqs || !route || !device || !tiles || !slots) return fail(P1HIP_ERR_ARGS, "null request or output array");
+  return guarded([&]() {
+    if (int rc = below_batch_check(reqs, n)) return rc;
+    Runtime& R = rt();
+    std::lock_guard<std::mutex> g(R.mu);  // the split setting is the open devices'
+    const bool split = R.devs.empty() ? !knob(kNoSplitKnob) : R.split;
+    const int path = (int)knob(kBelowPathKnob);
+    const uint64_t max_slice = knob(kBelowMaxSliceKnob);
+    const std::vector<BelowBReq> q = below_batch_reqs(reqs, n);
+    std::vector<int> routes;
+    std::vector<size_t> live;
+    std::vector<BelowWState> st;
+    beloww_routes(q, path, max_slice, routes, live, st);
+    for (size_t i = 0; i < n; ++i) {
+      route[i] = routes[i];
+      device[i] = -1;
+      tiles[i] = slots[i] = 0;
+    }
+    std::vector<BelowBItem> dense;
+    std::vector<BelowWItem> sparse;
+    std::string err = beloww_round_items(q.data(), live, st, path, max_slice, dense, sparse);
+    if (!err.empty()) return fail(P1HIP_ERR_HIP, err);
+    for (const BelowBLaunch& L : belowb_layout(dense, ndev))
+      for (size_t it : L.items) {
+        const size_t i = live[dense[it].req];
+        device[i] = L.device;
+        tiles[i] = dense[it].tiles;
+        slots[i] = dense[it].slots;
+      }
+    if (sparse.empty()) return P1HIP_OK;
+    std::vector<size_t> pending(sparse.size());
+    for (size_t s = 0; s < sparse.size(); ++s) pending[s] = s;
+    BelowWGroup G;
+    err = beloww_next_group(q.data(), live, sparse, pending, ndev, (uint32_t)knob(kWideMaxSegsKnob),
+                            knob(kWideMinFastThreadsKnob), split, kWideMaxTiles, G);
+    if (!err.empty()) return fail(P1HIP_ERR_ARGS, err);
+    for (size_t m = 0; m < G.members.size(); ++m) {
+      if (G.Y.route[m] != kWideRouteWide) continue;
+      const BelowWItem& it = sparse[G.members[m]];
+      const size_t i = live[it.req];
+      device[i] = G.Y.device[m];
+      tiles[i] = G.Y.tiles[m];
+      slots[i] = beloww_slots(it.hi - it.lo + 1, q[i].target, G.Y.tiles[m], knob(kBelowWideMaxSlotsKnob));
+    }
+    return P1HIP_OK;
+  });
+}
+
+int p1hip_get_below_wide_stats(p1hip_below_wide_stats_t* out) {
+  if (!out) return fail(P1HIP_ERR_ARGS, "null stats pointer");
+  Runtime& R = rt();
+  std::lock_guard<std::mutex> g(R.mu);
+  *out = R.fstats;
+  return P1HIP_OK;
+}
+
+int p1hip_below_filter(const uint64_t* part_hash, const uint64_t* part_nonce, size_t ntiles, const uint32_t* range_tile0,
+                       const uint32_t* range_ntiles, const uint32_t* req_range0, const uint64_t* targets,
+                       const uint32_t* req_slot0, size_t nreq, uint32_t* cand, uint32_t* count) {
+  if (nreq == 0) return P1HIP_OK;
+  if (!req_range0 || !req_slot0 || !targets || !count) return fail(P1HIP_ERR_ARGS, "null table, target or count array");
+  if (nreq > kWideMaxTiles || ntiles > kWideMaxTiles) return fail(P1HIP_ERR_ARGS, "too many requests or tiles");
+  // the kernel trusts its tables: every bound it relies on is checked here
+  if (req_range0[0] != 0 || req_slot0[0] != 0) return fail(P1HIP_ERR_ARGS, "a request table does not start at 0");
+  for (size_t r = 0; r < nreq; ++r)
+    if (req_range0[r + 1] < req_range0[r] || req_slot0[r + 1] < req_slot0[r])
+      return fail(P1HIP_ERR_ARGS, "request " + std::to_string(r) + ": a request table falls");
+  if (req_range0[nreq] > kWideMaxTiles || req_slot0[nreq] > kWideMaxTiles)
+    return fail(P1HIP_ERR_ARGS, "more than 2^24 ranges or slots");
+  if (req_range0[nreq] > 0 && (!range_tile0 || !range_ntiles)) return fail(P1HIP_ERR_ARGS, "null range table");
+  for (size_t j = 0; j < req_range0[nreq]; ++j)
+    if (range_tile0[j] > ntiles || range_ntiles[j] > ntiles - range_tile0[j])
+      return fail(P1HIP_ERR_ARGS, "range " + std::to_string(j) + " lies outside the partial array");
+  if ((ntiles > 0 && (!part_hash || !part_nonce)) || (!cand && req_slot0[nreq] > 0))
+    return fail(P1HIP_ERR_ARGS, "null partial or cand array");
+  return guarded([&]() {
+    return below_filter_locked(part_hash, part_nonce, ntiles, range_tile0, range_ntiles, req_range0, targets, req_slot0,
+                               nreq, cand, count);
+  });
 }
 
 int p1hip_scan_batch(const p1hip_request_t* reqs, size_t n, p1hip_result_t* out) {
@@ -2447,6 +3044,7 @@ void p1hip_reset_stats(void) {
   R.astats = p1hip_async_stats_t{};
   R.lstats = p1hip_below_stats_t{};
   R.qstats = p1hip_below_batch_stats_t{};
+  R.fstats = p1hip_below_wide_stats_t{};
   for (Dev& d : R.devs) {
     d.acc = p1hip_device_stats_t{};
     d.acc.shard_first = 1;  // empty until the next scan

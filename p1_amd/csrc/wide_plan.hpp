@@ -138,11 +138,14 @@ inline std::string wide_fill_launch(const WideDevice& D, const WideLaunch& W, Se
 //   wide_max   above that and at most this many: wide
 //   max_segs   segments per k_scan launch (kMaxSegs; tests cut launches small)
 //   fast_floor 0: wide_min_fast_threads per device; else the floor itself
+//   max_tiles  tiles of one device's partial array (kWideMaxTiles; tests cut it
+//              small so that requests are turned away for lack of room)
 // The wide requests are cut, in request order, into `ndev` contiguous groups
 // of near-equal predicted cost (a request goes to the device in whose share
 // of the cost its middle falls).  Returns "" or an error naming the request.
 inline std::string wide_layout(const BatchReq* reqs, size_t n, int ndev, uint64_t small_max, uint64_t wide_max,
-                               uint32_t max_segs, uint64_t fast_floor, bool split, WideLayout& Y) {
+                               uint32_t max_segs, uint64_t fast_floor, bool split, WideLayout& Y,
+                               uint64_t max_tiles = kWideMaxTiles) {
   Y = WideLayout();
   Y.route.assign(n, kWideRouteEmpty);
   Y.device.assign(n, -1);
@@ -188,7 +191,7 @@ inline std::string wide_layout(const BatchReq* reqs, size_t n, int ndev, uint64_
       Plan plan;
       const std::string err = make_plan(q.msg, q.len, q.lower, q.upper, plan, true, D.min_fast_threads, split, false);
       if (!err.empty()) return "request " + std::to_string(i) + ": planner: " + err;
-      if (tiles + plan.total_blocks > kWideMaxTiles) {
+      if (tiles + plan.total_blocks > max_tiles) {
         Y.route[i] = kWideRouteIndividual;
         Y.device[i] = -1;
         continue;

@@ -97,6 +97,8 @@ struct BelowHit {
 // job, in order, each what p1hip_scan_below returns for it.  A cap above the
 // number of nonces in the job's range is asked for as that number (a range
 // cannot hold more hits); the caps of one call may add up to at most 2^26.
-std::vector<std::vector<BelowHit>> BelowBatch(const std::vector<BelowJob>& jobs);
+// `wide`: through p1hip_scan_below_batch_wide, which also coalesces the jobs
+// with hard targets; the answers are the same.
+std::vector<std::vector<BelowHit>> BelowBatch(const std::vector<BelowJob>& jobs, bool wide = false);
 
 }  // namespace miner

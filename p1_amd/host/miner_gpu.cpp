@@ -4,7 +4,8 @@
 // the library; there is no CPU path.  HandleBatch answers many requests
 // through one p1hip_scan_batch (or p1hip_scan_batch_wide) call; AnswerPieces
 // is the backend of the multi-connection miner's rounds (miner_pool.hpp).
-// BelowBatch answers many target searches through one p1hip_scan_below_batch.
+// BelowBatch answers many target searches through one p1hip_scan_below_batch
+// (or, `wide`, p1hip_scan_below_batch_wide) call.
 #include <string>
 #include <vector>
 
@@ -80,7 +81,7 @@ std::vector<bitcoin::Message> HandleBatch(const std::vector<bitcoin::Message>& r
   return res;
 }
 
-std::vector<std::vector<BelowHit>> BelowBatch(const std::vector<BelowJob>& jobs) {
+std::vector<std::vector<BelowHit>> BelowBatch(const std::vector<BelowJob>& jobs, bool wide) {
   std::vector<p1hip_below_request_t> q;
   q.reserve(jobs.size());
   size_t total = 0;
@@ -94,8 +95,11 @@ std::vector<std::vector<BelowHit>> BelowBatch(const std::vector<BelowJob>& jobs)
   }
   std::vector<p1hip_result_t> hits(total);
   std::vector<size_t> found(q.size(), 0);
-  const int rc = p1hip_scan_below_batch(q.data(), q.size(), hits.data(), hits.size(), found.data());
-  if (rc != P1HIP_OK) throw bitcoin::HipError(rc, std::string("p1hip_scan_below_batch: ") + p1hip_last_error());
+  const int rc = wide ? p1hip_scan_below_batch_wide(q.data(), q.size(), hits.data(), hits.size(), found.data())
+                      : p1hip_scan_below_batch(q.data(), q.size(), hits.data(), hits.size(), found.data());
+  if (rc != P1HIP_OK)
+    throw bitcoin::HipError(rc, std::string(wide ? "p1hip_scan_below_batch_wide: " : "p1hip_scan_below_batch: ") +
+                                    p1hip_last_error());
   std::vector<std::vector<BelowHit>> out(q.size());
   size_t off = 0;
   for (size_t i = 0; i < q.size(); ++i) {

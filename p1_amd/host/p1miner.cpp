@@ -42,7 +42,7 @@
 //                                        p1hip_scan_below: one "Result <hash>
 //                                        <nonce>" line per hit in nonce order;
 //                                        exits 0 with no line when there is none
-//   p1miner below [--device N] [--batch B]
+//   p1miner below [--device N] [--batch B] [--hard]
 //                                        one target search per stdin line,
 //                                        "<msg-hex|-> <lower> <upper> <target>
 //                                        <cap>" ("-": the empty message); the
@@ -56,7 +56,10 @@
 //                                        <nonce>" in nonce order.  A line that
 //                                        does not parse ends the program with
 //                                        status 1 after the lines before it are
-//                                        answered.
+//                                        answered.  --hard: through
+//                                        p1hip_scan_below_batch_wide, which also
+//                                        coalesces the hard-target searches; the
+//                                        lines read and written are the same.
 //   p1miner hash <msg> <nonce>           prints bitcoin.Hash(msg, nonce)
 //   p1miner serve [--device N] [--chunk C] [--batch B [--wide]]
 //                                        one JSON Message per stdin line; every
@@ -103,7 +106,7 @@
 
 static int usage() {
   fprintf(stderr,
-          "usage: p1miner scan <msg> <lower> <upper> [--below <target> [--count N]] | below [--device N] [--batch B] | "
+          "usage: p1miner scan <msg> <lower> <upper> [--below <target> [--count N]] | below [--device N] [--batch B] [--hard] | "
           "hash <msg> <nonce> | "
           "serve [--device N] [--chunk C] [--batch B [--wide]] | lsp <host:port> [--device N] [--chunk C] [--epoch-limit K] "
           "[--epoch-millis M] [--window W] [--copies K] [--connect-copies K] "
@@ -174,7 +177,7 @@ static bool parse_below_line(const std::string& line, miner::BelowJob* job) {
 // p1miner below: batches of target searches through miner::BelowBatch.  The
 // device is opened by the first batch that needs one (or, with --device, by
 // the first batch).
-static int run_below_batches(int dev, uint64_t batch) {
+static int run_below_batches(int dev, uint64_t batch, bool wide) {
   std::vector<miner::BelowJob> jobs;
   bool opened = false;
   auto flush = [&]() -> bool {
@@ -185,7 +188,7 @@ static int run_below_batches(int dev, uint64_t batch) {
       }
       opened = true;
     }
-    for (const std::vector<miner::BelowHit>& hits : miner::BelowBatch(jobs)) {
+    for (const std::vector<miner::BelowHit>& hits : miner::BelowBatch(jobs, wide)) {
       printf("Hits %zu\n", hits.size());
       for (const miner::BelowHit& h : hits) printf("Result %" PRIu64 " %" PRIu64 "\n", h.hash, h.nonce);
     }
@@ -339,12 +342,14 @@ int main(int argc, char** argv) {
     if (cmd == "below") {
       int dev = -1;
       uint64_t batch = 256, d = 0;
+      bool wide = false;
       for (int i = 2; i < argc; ++i) {
         if (!strcmp(argv[i], "--device") && i + 1 < argc) { if (!parse_u64(argv[++i], &d) || d > 1023) return usage(); dev = (int)d; }
         else if (!strcmp(argv[i], "--batch") && i + 1 < argc) { if (!parse_u64(argv[++i], &batch) || batch == 0) return usage(); }
+        else if (!strcmp(argv[i], "--hard")) wide = true;  // `below --wide` stays a usage error
         else return usage();
       }
-      return run_below_batches(dev, batch);
+      return run_below_batches(dev, batch, wide);
     }
     if (cmd == "hash" && argc == 4) {
       uint64_t n;
